@@ -15,9 +15,9 @@ _88 set + 1809 in the _96 set of 2000 frames).
 
 Pipeline, all on the device: hpe_blazeface_forward (taps written once, in HBM) -> hpe_forward of
 the two embedded regressors -> hpe_detect (threshold, decode, NMS) -> hpe_gather_features.  Frames
-must already be the model input (``prepareInputForInference``, blazeFaceDetectorH5.py:244-269:
-bicubic resize to 128x128 and (x/255 - 0.5)/0.5 are the caller's; the image decoders, cv2 and
-tf.image are not part of this image).
+are either the prepared float model input or raw uint8 camera frames, which hpe_preprocess prepares
+on the device first (``prepareInputForInference``, blazeFaceDetectorH5.py:247-269: RGB, /255, bicubic
+resize to 128x128, (x - 0.5) / 0.5; hpe.preprocess), batch by batch.  Image decoding is the caller's.
 """
 import ctypes
 import os
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .detector import BlazeFaceDetector
+from .detector import BlazeFaceDetector, is_uint8
 
 
 def _ptr(t):
@@ -63,12 +63,16 @@ class FeatureExtractor:
         m = load_model(path, compile=False)
         return cls(m.model_config, m.weights_dict(), **kw)
 
-    def extract_device(self, frames):
-        """frames (n,128,128,3) on the device -> dict of device tensors: feat88 (n,k,C0),
-        feat96 (n,k,C1), src (n,k) int32 (0 front / 1 back / -1 none), plus the detector outputs."""
+    def extract_device(self, frames, bgr=True, crop=None):
+        """frames (n,128,128,3) prepared float input, or raw uint8 frames (n,H,W,3) (``bgr`` / ``crop``
+        as hpe.preprocess.prepare_input) -> dict of device tensors: feat88 (n,k,C0), feat96 (n,k,C1),
+        src (n,k) int32 (0 front / 1 back / -1 none), plus the detector outputs."""
         net, dev = self.det.net, self.det.device
-        x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
-        x = x.to(dev, torch.float32).contiguous()
+        if is_uint8(frames):
+            x = self.det.prepare(frames, bgr=bgr, crop=crop)
+        else:
+            x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
+            x = x.to(dev, torch.float32).contiguous()
         n = x.shape[0]
         r = self.det.postprocess(net.forward(x))
         k = self.max_faces
@@ -85,13 +89,14 @@ class FeatureExtractor:
         r.update(feat88=f0, feat96=f1, src=src)
         return r
 
-    def extract(self, frames, batch_size=1024):
+    def extract(self, frames, batch_size=1024, bgr=True, crop=None):
         """Host arrays: (features_front (m0,C0), frame index (m0,), features_back (m1,C1), frame
-        index (m1,)) in frame order, detections in NMS order within a frame."""
+        index (m1,)) in frame order, detections in NMS order within a frame.  uint8 frames are
+        prepared on the device one ``batch_size`` slice at a time."""
         fr, ir, bk, ib = [], [], [], []
         n = len(frames)
         for s in range(0, n, batch_size):
-            r = self.extract_device(frames[s:s + batch_size])
+            r = self.extract_device(frames[s:s + batch_size], bgr=bgr, crop=crop)
             src = r['src'].cpu().numpy()
             f0 = r['feat88'].cpu().numpy()
             f1 = r['feat96'].cpu().numpy()
@@ -110,14 +115,14 @@ class FeatureExtractor:
         return ('%s_features_%d_%s_%d.npz' % (prefix, self.c_front, t, self.max_faces),
                 '%s_features_%d_%s_%d.npz' % (prefix, self.c_back, t, self.max_faces))
 
-    def build_datasets(self, frames, poses, prefix, batch_size=1024):
+    def build_datasets(self, frames, poses, prefix, batch_size=1024, bgr=True, crop=None):
         """Write <prefix>_features_88_<t>_<k>.npz and <prefix>_features_96_<t>_<k>.npz (keys
         ``features`` float32, ``poses`` float64 yaw/pitch/roll of the frame); returns the paths."""
         poses = np.asarray(poses, np.float64).reshape(-1, 3)
         if len(poses) != len(frames):
             raise ValueError('need one (yaw, pitch, roll) per frame: %d frames, %d poses'
                              % (len(frames), len(poses)))
-        f0, i0, f1, i1 = self.extract(frames, batch_size)
+        f0, i0, f1, i1 = self.extract(frames, batch_size, bgr=bgr, crop=crop)
         p0, p1 = self.dataset_names(prefix)
         d = os.path.dirname(p0)
         if d:

@@ -236,6 +236,22 @@ int hpe_gather_features(const int32_t *count, const int32_t *det_index, int64_t 
                         int32_t k, const float *tap0, int32_t c0, const float *tap1, int32_t c1, float *feat0,
                         float *feat1, int32_t *src, void *stream);
 
+/* Raw camera frames -> network input (csrc/hpe_preproc.hip), replacing prepareInputForInference
+ * (BlazePoser/blazeFaceDetectorH5.py:247-269: cv2.COLOR_BGR2RGB, / 255.0, tf.image.resize(method=
+ * 'bicubic') to the model input, (x - 0.5) / 0.5) for a whole batch in one launch.
+ * frames: n device images of in_h x in_w x 3 bytes, rows row_stride_bytes apart (>= 3 * in_w), frames
+ * in_h * row_stride_bytes apart.  The crop rectangle (crop_x0, crop_y0, crop_w, crop_h), which must lie
+ * inside the frame, is what gets resized (the webcam loop's centre crop, :394-399).  bgr != 0 reverses
+ * the channel order.  out: (n, out_h, out_w, 3) fp32 RGB in [-1, 1] up to the bicubic overshoot —
+ * the `images` argument of hpe_blazeface_forward.
+ * Arithmetic: TF 2.x ResizeBicubic with half_pixel_centers (Keys cubic A = -0.5 through a 1/1024
+ * weight table, taps clamped to the crop, clamped taps dropped and the rest renormalised), every
+ * fp32 operation rounded on its own (no FMA contraction), tap value (float)((double)byte / 255.0);
+ * tests/bicubic_ref.py restates it bit for bit.  n * out_h * out_w must fit int32; n == 0 is a no-op. */
+int hpe_preprocess(const uint8_t *frames, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
+                   int32_t crop_x0, int32_t crop_y0, int32_t crop_w, int32_t crop_h, int32_t bgr,
+                   float *out, int32_t out_h, int32_t out_w, void *stream);
+
 const char *hpe_last_error(void);
 
 /* Build stamp: "src=<sha256/16 of the library's sources> git=<commit>[-dirty]" (csrc/Makefile).  The
