@@ -11,6 +11,8 @@
 // Every fp32 operation is rounded on its own: the file is compiled with contraction off, so no
 // multiply-add pair becomes an FMA (the only fused ops left are inside the division expansions).
 // One thread per output pixel (three channels), lanes along x; a gather bounded by load latency.
+// Below it: the same preparation per row of a device table of regions of interest that may reach
+// outside the frame (hpe_preprocess_rois), and the table of a second detector pass (hpe_face_rois).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -172,5 +174,256 @@ extern "C" int hpe_preprocess(const uint8_t* frames, int64_t n, int32_t in_h, in
   hipLaunchKernelGGL(preprocess_kernel, dim3(grid), dim3(PRE_T), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_preprocess launch: %s", hipGetErrorString(e));
+  return HPE_OK;
+}
+
+// ---- per-row regions of interest ------------------------------------------------------------------
+// hpe_preprocess_rois: output r is hpe_preprocess of a whole h x w canvas whose pixel (y, x) is the
+// frame's pixel (y0 + y, x0 + x) where that lies inside the frame and the pad bytes elsewhere, for row
+// r = (frame, x0, y0, w, h) of a device table.  Same arithmetic in the same order as preprocess_kernel
+// (taps clamp to the canvas, not to the frame), so an ROI inside the frame equals hpe_preprocess with
+// that crop and an ROI reaching outside equals hpe_preprocess on a host-padded copy, bit for bit.
+#define ROI_LIM (1 << 24)   // |x0|, |y0|, w, h <= 2^24: every coordinate sum below fits int32
+
+struct RoiArgs {
+  const uint8_t* frames;
+  const int32_t* rois;     // (m, 5): frame, x0, y0, w, h
+  float* out;
+  int64_t frame_stride, row_stride;   // bytes
+  int n_frames, in_w, in_h, out_w, out_h;
+  int total;               // m * out_h * out_w
+  int bgr;
+  int pad0, pad1, pad2;    // pad bytes in the frame's channel order
+};
+
+__global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);
+  __syncthreads();
+  const int64_t gid = (int64_t)blockIdx.x * PRE_T + threadIdx.x;
+  if (gid >= a.total) return;
+  const int pix = (int)gid;
+  const int ox = pix % a.out_w;
+  const int row = pix / a.out_w;
+  const int oy = row % a.out_h;
+  const int64_t r = row / a.out_h;
+
+  const int32_t* roi = a.rois + r * 5;
+  const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
+  float* dst = a.out + (int64_t)pix * 3;
+  const uint8_t pad[3] = {(uint8_t)a.pad0, (uint8_t)a.pad1, (uint8_t)a.pad2};
+  const bool valid = fr >= 0 && fr < a.n_frames && cw >= 1 && cw <= ROI_LIM && ch >= 1 && ch <= ROI_LIM &&
+                     x0 >= -ROI_LIM && x0 <= ROI_LIM && y0 >= -ROI_LIM && y0 <= ROI_LIM;
+  if (!valid) {   // reads no frame memory
+    float o[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
+    dst[0] = a.bgr ? o[2] : o[0];
+    dst[1] = o[1];
+    dst[2] = a.bgr ? o[0] : o[2];
+    return;
+  }
+
+  int yi[4], xi[4];
+  float wy[4], wx[4];
+  taps(oy, (float)ch / (float)a.out_h, ch, yi, wy);
+  taps(ox, (float)cw / (float)a.out_w, cw, xi, wx);
+  // frame coordinates of the taps (ascending along each axis, as the clamped canvas indices are)
+  int fy[4], fx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    fy[k] = y0 + yi[k];
+    fx[k] = x0 + xi[k];
+  }
+  const bool x_in = fx[0] >= 0 && fx[3] < a.in_w;
+  const bool y_in = fy[0] >= 0 && fy[3] < a.in_h;
+  // the whole 4 x 4 window inside the frame and no x tap clamped: 12 contiguous bytes per row
+  const bool interior = x_in && y_in && xi[3] - xi[0] == 3;
+
+  const uint8_t* base = a.frames + (int64_t)fr * a.frame_stride;
+  uint8_t b[4][12];
+  if (interior) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const u32u* q = (const u32u*)(base + (int64_t)fy[j] * a.row_stride + fx[0] * 3);
+      const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        b[j][e] = (uint8_t)(q0 >> (8 * e));
+        b[j][4 + e] = (uint8_t)(q1 >> (8 * e));
+        b[j][8 + e] = (uint8_t)(q2 >> (8 * e));
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool row_in = fy[j] >= 0 && fy[j] < a.in_h;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (row_in && fx[k] >= 0 && fx[k] < a.in_w) {
+          const uint8_t* p = base + (int64_t)fy[j] * a.row_stride + fx[k] * 3;
+          b[j][3 * k] = p[0];
+          b[j][3 * k + 1] = p[1];
+          b[j][3 * k + 2] = p[2];
+        } else {
+          b[j][3 * k] = pad[0];
+          b[j][3 * k + 1] = pad[1];
+          b[j][3 * k + 2] = pad[2];
+        }
+      }
+    }
+  }
+  float c[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) {
+    c[e] = lut[b[0][e]] * wy[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) c[e] = c[e] + lut[b[j][e]] * wy[j];
+  }
+  float o[3];
+#pragma unroll
+  for (int cc = 0; cc < 3; ++cc) {
+    const float v = ((c[cc] * wx[0] + c[3 + cc] * wx[1]) + c[6 + cc] * wx[2]) + c[9 + cc] * wx[3];
+    o[cc] = (v - 0.5f) / 0.5f;
+  }
+  dst[0] = a.bgr ? o[2] : o[0];
+  dst[1] = o[1];
+  dst[2] = a.bgr ? o[0] : o[2];
+}
+
+extern "C" int hpe_preprocess_rois(const uint8_t* frames, int64_t n_frames, int32_t in_h, int32_t in_w,
+                                   int64_t row_stride_bytes, const int32_t* rois, int64_t m, int32_t pad_b0,
+                                   int32_t pad_b1, int32_t pad_b2, int32_t bgr, float* out, int32_t out_h,
+                                   int32_t out_w, void* stream) {
+  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: negative frame or ROI count");
+  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: sizes must be positive (frame %d x %d, out %d x %d)", in_h, in_w,
+                    out_h, out_w);
+  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: frame width %d too large", in_w);
+  if (row_stride_bytes < 3 * (int64_t)in_w)
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: row stride %lld below 3 * in_w = %lld",
+                    (long long)row_stride_bytes, 3 * (long long)in_w);
+  if (n_frames > 0x7fffffff || row_stride_bytes > INT64_MAX / in_h ||
+      (n_frames > 0 && row_stride_bytes * in_h > INT64_MAX / n_frames))
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: batch too large");
+  if (pad_b0 < 0 || pad_b0 > 255 || pad_b1 < 0 || pad_b1 > 255 || pad_b2 < 0 || pad_b2 > 255)
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: pad bytes (%d, %d, %d) outside 0..255", pad_b0, pad_b1, pad_b2);
+  if (m > 0 && m > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: m * out_h * out_w exceeds INT32_MAX");
+  if (m == 0) return HPE_OK;
+  // without frames every row is invalid and nothing is read through `frames`
+  if ((!frames && n_frames > 0) || !rois || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: null argument");
+  RoiArgs a;
+  a.frames = frames;
+  a.rois = rois;
+  a.out = out;
+  a.frame_stride = (int64_t)in_h * row_stride_bytes;
+  a.row_stride = row_stride_bytes;
+  a.n_frames = (int)n_frames;
+  a.in_w = in_w;
+  a.in_h = in_h;
+  a.out_w = out_w;
+  a.out_h = out_h;
+  a.total = (int)(m * out_h * out_w);
+  a.bgr = bgr;
+  a.pad0 = pad_b0;
+  a.pad1 = pad_b1;
+  a.pad2 = pad_b2;
+  const unsigned grid = (unsigned)(((int64_t)a.total + PRE_T - 1) / PRE_T);
+  hipLaunchKernelGGL(preprocess_rois_kernel, dim3(grid), dim3(PRE_T), 0, (hipStream_t)stream, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_preprocess_rois launch: %s", hipGetErrorString(e));
+  return HPE_OK;
+}
+
+// hpe_face_rois: hpe_detect's boxes -> the ROI table of a second pass.  One workgroup per frame: the
+// row offset of frame i is the sum of count[0 .. i) (a block reduction, so the compaction is
+// deterministic), and the slots past the total are filled with the invalid row.  float64, every
+// operation rounded on its own (contraction is off in this file).
+#define FROI_T 256
+
+__device__ __forceinline__ int froi_count(const int32_t* count, int64_t i, int max_faces) {
+  return min(max(count[i], 0), max_faces);
+}
+
+__global__ void __launch_bounds__(FROI_T) face_rois_kernel(const int32_t* count, const double* boxes, int n_images,
+                                                            int max_faces, double sx0, double sy0, double sw,
+                                                            double sh, double scale, int32_t* rois,
+                                                            int32_t* n_rois) {
+  __shared__ int red[2][FROI_T];
+  const int img = blockIdx.x;
+  const int t = threadIdx.x;
+  int before = 0, all = 0;
+  for (int i = t; i < n_images; i += FROI_T) {
+    const int c = froi_count(count, i, max_faces);
+    all += c;
+    if (i < img) before += c;
+  }
+  red[0][t] = before;
+  red[1][t] = all;
+  __syncthreads();
+  for (int s = FROI_T / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      red[0][t] += red[0][t + s];
+      red[1][t] += red[1][t + s];
+    }
+    __syncthreads();
+  }
+  const int64_t first = red[0][0], total = red[1][0];
+  if (img == 0 && t == 0) *n_rois = (int32_t)total;
+  const int c = froi_count(count, img, max_faces);
+  for (int j = t; j < max_faces; j += FROI_T) {
+    if (j < c) {
+      const double* bo = boxes + ((int64_t)img * max_faces + j) * 4;
+      const double px1 = sx0 + bo[0] * sw, py1 = sy0 + bo[1] * sh;
+      const double px2 = sx0 + bo[2] * sw, py2 = sy0 + bo[3] * sh;
+      const double cx = 0.5 * (px1 + px2), cy = 0.5 * (py1 + py2);
+      const double side = scale * fmax(px2 - px1, py2 - py1);
+      int32_t* o = rois + (first + j) * 5;
+      if (isfinite(cx) && isfinite(cy) && isfinite(side)) {
+        const double lim = (double)ROI_LIM;
+        const double S = fmin(fmax(ceil(side), 1.0), lim);
+        const double rx = fmin(fmax(floor(cx - 0.5 * S), -lim), lim);
+        const double ry = fmin(fmax(floor(cy - 0.5 * S), -lim), lim);
+        o[0] = img;
+        o[1] = (int32_t)rx;
+        o[2] = (int32_t)ry;
+        o[3] = (int32_t)S;
+        o[4] = (int32_t)S;
+      } else {
+        o[0] = -1;
+        o[1] = o[2] = o[3] = o[4] = 0;
+      }
+    }
+    // the tail: slots [total, n_images * max_faces), each written by the block that owns its index
+    const int64_t slot = (int64_t)img * max_faces + j;
+    if (slot >= total) {
+      int32_t* o = rois + slot * 5;
+      o[0] = -1;
+      o[1] = o[2] = o[3] = o[4] = 0;
+    }
+  }
+}
+
+extern "C" int hpe_face_rois(const int32_t* count, const double* boxes, int64_t n_images, int32_t max_faces,
+                             int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h, double scale,
+                             int32_t* rois, int32_t* n_rois, void* stream) {
+  if (n_images < 0) return hpe_fail(HPE_EINVAL, "hpe_face_rois: negative frame count");
+  if (max_faces <= 0) return hpe_fail(HPE_EINVAL, "hpe_face_rois: max_faces must be positive");
+  if (src_w <= 0 || src_h <= 0)
+    return hpe_fail(HPE_EINVAL, "hpe_face_rois: source rectangle %d x %d must be positive", src_w, src_h);
+  if (n_images > (int64_t)0x7fffffff / max_faces) return hpe_fail(HPE_EINVAL, "hpe_face_rois: batch too large");
+  if (!n_rois || (n_images > 0 && (!count || !boxes || !rois)))
+    return hpe_fail(HPE_EINVAL, "hpe_face_rois: null argument");
+  if (n_images == 0) {
+    const hipError_t e = hipMemsetAsync(n_rois, 0, sizeof(int32_t), (hipStream_t)stream);
+    if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_face_rois memset: %s", hipGetErrorString(e));
+    return HPE_OK;
+  }
+  hipLaunchKernelGGL(face_rois_kernel, dim3((unsigned)n_images), dim3(FROI_T), 0, (hipStream_t)stream, count, boxes,
+                     (int)n_images, (int)max_faces, (double)src_x0, (double)src_y0, (double)src_w, (double)src_h,
+                     scale, rois, n_rois);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_face_rois launch: %s", hipGetErrorString(e));
   return HPE_OK;
 }

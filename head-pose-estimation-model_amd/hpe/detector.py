@@ -6,8 +6,10 @@ one frame and ``detect_batch(frames)`` for a batch, returning ``Results(boxes, k
 poses)`` per frame (:359-364).  uint8 input is a raw camera frame, as the reference's ``detectFaces``
 takes it (BGR): ``detect_images`` prepares it on the device (``prepareInputForInference``, :247-269:
 RGB, /255, bicubic resize to 128x128, (x - 0.5) / 0.5 — hpe.preprocess, csrc/hpe_preproc.hip).  Float
-input is the already prepared model input.  ``EMAFilter`` is the webcam loop's pose smoothing
-(:16-35); webcam capture and drawing are out of scope.
+input is the already prepared model input.  ``detect_rois`` runs the detector on regions of interest of
+the frames (hpe_preprocess_rois) and ``detect_refine`` looks a second time at an enlarged square around
+every face of a first pass (hpe_face_rois); neither is in the reference.  ``EMAFilter`` is the webcam
+loop's pose smoothing (:16-35); webcam capture and drawing are out of scope.
 """
 import ctypes
 import math
@@ -17,7 +19,7 @@ import torch
 
 from . import _lib
 from .blazeface import BlazeFace
-from .preprocess import prepare_input
+from .preprocess import _checked_frames, _device_frames, crop_rect, prepare_input, prepare_rois
 
 KEY_POINT_SIZE = 6      # blazeFaceDetectorH5.py:8
 MAX_FACE_NUM = 100      # blazeFaceDetectorH5.py:9
@@ -29,6 +31,7 @@ class Results:
         self.keypoints = keypoints
         self.scores = scores
         self.poses = poses
+        self.refined = np.zeros(len(scores), bool)   # detect_refine: the second pass replaced this face
 
 
 class EMAFilter:
@@ -55,6 +58,13 @@ def is_uint8(frames):
     if torch.is_tensor(frames):
         return frames.dtype == torch.uint8
     return isinstance(frames, np.ndarray) and frames.dtype == np.uint8
+
+
+def remap_roi(xy, rx, ry, side, src):
+    """(..., 2) float64 points normalised to the square ROI (rx, ry, side) -> normalised to the source
+    rectangle src = (x0, y0, w, h): X = (rx + x * side - x0) / w, likewise in y."""
+    xy = np.asarray(xy, np.float64)
+    return np.stack([(rx + xy[..., 0] * side - src[0]) / src[2], (ry + xy[..., 1] * side - src[1]) / src[3]], -1)
 
 
 def _ptr(t):
@@ -125,6 +135,65 @@ class BlazeFaceDetector:
             return self.detect_images(frames)
         x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
         return self._results(x.to(self.device, torch.float32))
+
+    def detect_rois(self, frames, rois, bgr=True, pad_value=0):
+        """frames: raw uint8 frames; rois: (m, 5) rows of (frame, x0, y0, w, h) in frame pixels, which
+        may reach outside the frame (``pad_value`` there), as hpe.preprocess.prepare_rois -> [Results]
+        * m, boxes and keypoints normalised to each ROI: what detect_batch returns for the prepared
+        ROI images."""
+        x = prepare_rois(frames, rois, size=tuple(self.net.structure['input_hw']), bgr=bgr,
+                         pad_value=pad_value, device=self.device)
+        return self._results(x) if x.shape[0] else []
+
+    def face_rois(self, r, src, scale):
+        """r: postprocess() outputs; src: the first pass's source rectangle (x0, y0, w, h) in frame
+        pixels -> (rois (n * max_faces, 5) int32, n_rois (1,) int32) on the device (hpe_face_rois): an
+        enlarged square around every face, frame-major in NMS order."""
+        n = r['count'].shape[0]
+        rois = torch.empty((n * self.max_faces, 5), dtype=torch.int32, device=self.device)
+        n_rois = torch.zeros(1, dtype=torch.int32, device=self.device)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.hpe_face_rois(_ptr(r['count']), _ptr(r['boxes']), n, self.max_faces, int(src[0]),
+                                         int(src[1]), int(src[2]), int(src[3]), float(scale), _ptr(rois),
+                                         _ptr(n_rois), stream), 'hpe_face_rois')
+        return rois, n_rois
+
+    def detect_refine(self, frames, scale, bgr=True, crop=None, pad_value=0):
+        """Detect, then look again at an enlarged square around every face: the first pass as
+        detect_images, the ROI table on the device (side = scale x the box's longer side in frame
+        pixels; ``scale`` has no measured default), one host read of the ROI count, the second pass
+        as detect_rois.  Returns one Results per frame with the first pass's faces in the first
+        pass's order.  Where the second pass found anything in a face's ROI, its top-scoring detection
+        replaces score, pose, box and keypoints (mapped back to the first pass's normalisation, in
+        float64 on the host) and ``refined`` is True; otherwise the first-pass values stay."""
+        x, _ = _device_frames(_checked_frames(frames, 'detect_refine'), self.device, None, 'detect_refine')
+        src = crop_rect(x.shape[1], x.shape[2], crop)
+        r = self.postprocess(self.net.forward(self.prepare(x, bgr=bgr, crop=crop)))
+        rois, n_rois = self.face_rois(r, src, scale)
+        m = int(n_rois.item())
+        h = {k: v.cpu().numpy() for k, v in r.items()}
+        second = self.detect_rois(x, rois[:m], bgr=bgr, pad_value=pad_value) if m else []
+        table = rois[:m].cpu().numpy()
+        res, row = [], 0
+        for i in range(x.shape[0]):
+            c = int(h['count'][i])
+            out = Results(h['boxes'][i, :c].copy(), h['keypoints'][i, :c].copy(), h['scores'][i, :c].copy(),
+                          h['poses'][i, :c].copy() if c else np.zeros((0, 3), np.float32))
+            for j in range(c):
+                fr, rx, ry, side, _ = (int(v) for v in table[row])
+                s2 = second[row]
+                row += 1
+                if fr < 0 or not len(s2.scores):
+                    continue
+                out.scores[j] = s2.scores[0]
+                out.poses[j] = s2.poses[0]
+                out.boxes[j] = remap_roi(s2.boxes[0].reshape(2, 2), rx, ry, side, src).reshape(4)
+                out.keypoints[j] = remap_roi(s2.keypoints[0], rx, ry, side, src)
+                out.refined[j] = True
+            res.append(out)
+        return res
 
     def detectFaces(self, frame):
         if is_uint8(frame):

@@ -18,6 +18,12 @@ the two embedded regressors -> hpe_detect (threshold, decode, NMS) -> hpe_gather
 are either the prepared float model input or raw uint8 camera frames, which hpe_preprocess prepares
 on the device first (``prepareInputForInference``, blazeFaceDetectorH5.py:247-269: RGB, /255, bicubic
 resize to 128x128, (x - 0.5) / 0.5; hpe.preprocess), batch by batch.  Image decoding is the caller's.
+
+``rois=`` runs the same pipeline on regions of interest of uint8 frames instead of whole frames
+(hpe_preprocess_rois): rows (frame, x0, y0, w, h) that may reach outside the frame, ``pad_value``
+there.  That is the mechanism for the reference's ``*_Enlarged_features_*`` sets, whose frames were
+placed on a larger canvas; what the out-of-repo extractor did exactly (canvas size, pad colour) is
+unknown, so their recipe stays unpinned.  Features of an ROI pass are indexed by ROI row.
 """
 import ctypes
 import os
@@ -27,6 +33,7 @@ import torch
 
 from . import _lib
 from .detector import BlazeFaceDetector, is_uint8
+from .preprocess import prepare_rois, roi_table
 
 
 def _ptr(t):
@@ -63,12 +70,19 @@ class FeatureExtractor:
         m = load_model(path, compile=False)
         return cls(m.model_config, m.weights_dict(), **kw)
 
-    def extract_device(self, frames, bgr=True, crop=None):
+    def extract_device(self, frames, bgr=True, crop=None, rois=None, pad_value=0):
         """frames (n,128,128,3) prepared float input, or raw uint8 frames (n,H,W,3) (``bgr`` / ``crop``
         as hpe.preprocess.prepare_input) -> dict of device tensors: feat88 (n,k,C0), feat96 (n,k,C1),
-        src (n,k) int32 (0 front / 1 back / -1 none), plus the detector outputs."""
+        src (n,k) int32 (0 front / 1 back / -1 none), plus the detector outputs.  With ``rois`` ((m, 5)
+        rows of (frame, x0, y0, w, h), ``pad_value`` outside the frame: hpe.preprocess.prepare_rois)
+        the inputs are the m regions of the uint8 frames and n = m."""
         net, dev = self.det.net, self.det.device
-        if is_uint8(frames):
+        if rois is not None:
+            if not is_uint8(frames) or crop is not None:
+                raise ValueError('rois= takes raw uint8 frames and no crop=')
+            x = prepare_rois(frames, rois, size=tuple(net.structure['input_hw']), bgr=bgr, pad_value=pad_value,
+                             device=dev)
+        elif is_uint8(frames):
             x = self.det.prepare(frames, bgr=bgr, crop=crop)
         else:
             x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
@@ -89,14 +103,31 @@ class FeatureExtractor:
         r.update(feat88=f0, feat96=f1, src=src)
         return r
 
-    def extract(self, frames, batch_size=1024, bgr=True, crop=None):
+    def _roi_batch(self, frames, rois, bgr, pad_value):
+        """One slice of a host ROI table: only the frames its valid rows name are handed on."""
+        rois = rois.copy()
+        ok = (rois[:, 0] >= 0) & (rois[:, 0] < len(frames))
+        rois[~ok, 0] = -1
+        lo, hi = (int(rois[ok, 0].min()), int(rois[ok, 0].max()) + 1) if ok.any() else (0, min(1, len(frames)))
+        rois[ok, 0] -= lo
+        return self.extract_device(frames[lo:hi], bgr=bgr, rois=rois, pad_value=pad_value)
+
+    def extract(self, frames, batch_size=1024, bgr=True, crop=None, rois=None, pad_value=0):
         """Host arrays: (features_front (m0,C0), frame index (m0,), features_back (m1,C1), frame
         index (m1,)) in frame order, detections in NMS order within a frame.  uint8 frames are
-        prepared on the device one ``batch_size`` slice at a time."""
+        prepared on the device one ``batch_size`` slice at a time.  With ``rois`` (a host (m, 5) table,
+        as extract_device) the slices are of ROI rows and the two index arrays are ROI rows."""
         fr, ir, bk, ib = [], [], [], []
-        n = len(frames)
+        if rois is not None:
+            if crop is not None:
+                raise ValueError('rois= takes no crop=')
+            rois = roi_table(rois.cpu() if torch.is_tensor(rois) else rois).numpy()
+        n = len(frames) if rois is None else len(rois)
         for s in range(0, n, batch_size):
-            r = self.extract_device(frames[s:s + batch_size], bgr=bgr, crop=crop)
+            if rois is None:
+                r = self.extract_device(frames[s:s + batch_size], bgr=bgr, crop=crop)
+            else:
+                r = self._roi_batch(frames, rois[s:s + batch_size], bgr, pad_value)
             src = r['src'].cpu().numpy()
             f0 = r['feat88'].cpu().numpy()
             f1 = r['feat96'].cpu().numpy()
@@ -115,14 +146,20 @@ class FeatureExtractor:
         return ('%s_features_%d_%s_%d.npz' % (prefix, self.c_front, t, self.max_faces),
                 '%s_features_%d_%s_%d.npz' % (prefix, self.c_back, t, self.max_faces))
 
-    def build_datasets(self, frames, poses, prefix, batch_size=1024, bgr=True, crop=None):
+    def build_datasets(self, frames, poses, prefix, batch_size=1024, bgr=True, crop=None, rois=None,
+                       pad_value=0):
         """Write <prefix>_features_88_<t>_<k>.npz and <prefix>_features_96_<t>_<k>.npz (keys
-        ``features`` float32, ``poses`` float64 yaw/pitch/roll of the frame); returns the paths."""
+        ``features`` float32, ``poses`` float64 yaw/pitch/roll of the frame); returns the paths.  With
+        ``rois`` (as extract) a row's pose is that of the frame its ROI names."""
         poses = np.asarray(poses, np.float64).reshape(-1, 3)
         if len(poses) != len(frames):
             raise ValueError('need one (yaw, pitch, roll) per frame: %d frames, %d poses'
                              % (len(frames), len(poses)))
-        f0, i0, f1, i1 = self.extract(frames, batch_size, bgr=bgr, crop=crop)
+        f0, i0, f1, i1 = self.extract(frames, batch_size, bgr=bgr, crop=crop, rois=rois, pad_value=pad_value)
+        if rois is not None:       # ROI rows -> frames; a detection in an invalid row's pad image has no pose
+            fr = roi_table(rois.cpu() if torch.is_tensor(rois) else rois).numpy()[:, 0]
+            k0, k1 = ((fr[i] >= 0) & (fr[i] < len(frames)) for i in (i0, i1))
+            f0, i0, f1, i1 = f0[k0], fr[i0][k0], f1[k1], fr[i1][k1]
         p0, p1 = self.dataset_names(prefix)
         d = os.path.dirname(p0)
         if d:

@@ -1,8 +1,10 @@
 """Raw camera frames -> network input on the GPU: ``prepareInputForInference`` of
 BlazePoser/blazeFaceDetectorH5.py:247-269 (cv2.COLOR_BGR2RGB, / 255.0, tf.image.resize(method=
 'bicubic'), (x - 0.5) / 0.5) for a batch of uint8 frames in one kernel (csrc/hpe_preproc.hip, C ABI
-``hpe_preprocess``).  The frames are uploaded as bytes; everything after the upload stays on the
-device.  Image decoding, webcam capture and drawing stay out of scope.
+``hpe_preprocess``), and the same per region of interest (``prepare_rois``, C ABI
+``hpe_preprocess_rois``): many rectangles per frame, which may reach outside it.  The frames are
+uploaded as bytes; everything after the upload stays on the device.  Image decoding, webcam capture
+and drawing stay out of scope.
 """
 import ctypes
 
@@ -27,17 +29,18 @@ def crop_rect(h, w, crop):
     return tuple(int(c) for c in crop)
 
 
-def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
-    """frames: uint8 (H, W, 3) or (n, H, W, 3), numpy array or tensor, host or device.  size: int or
-    (h, w) of the network input (128: front model, 256: back model).  bgr: the input is BGR (cv2
-    frames) and is reversed to RGB.  Returns the device tensor (n, h, w, 3) float32 (``out`` if given).
-    A device tensor whose pixels are contiguous is read in place through its row stride."""
+def _checked_frames(frames, what):
     x = frames if torch.is_tensor(frames) else np.asarray(frames)
     if x.dtype != (torch.uint8 if torch.is_tensor(x) else np.uint8):
-        raise ValueError('prepare_input takes uint8 frames, got %s' % (x.dtype,))
+        raise ValueError('%s takes uint8 frames, got %s' % (what, x.dtype))
     if x.ndim not in (3, 4) or x.shape[-1] != 3:
         raise ValueError('frames must be (H, W, 3) or (n, H, W, 3), got %s' % (tuple(x.shape),))
-    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    return x
+
+
+def _device_frames(x, device, out, what):
+    """checked uint8 (H, W, 3) / (n, H, W, 3) frames -> (the (n, H, W, 3) device tensor, its row stride
+    in bytes).  A device tensor whose pixels are contiguous is read in place through its row stride."""
     if not torch.is_tensor(x):
         x = torch.from_numpy(np.ascontiguousarray(x))
     if x.dim() == 3:
@@ -46,21 +49,91 @@ def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
         device = x.device if x.is_cuda else (out.device if out is not None else 'cuda')
     x = x.to(device)
     if x.device.type != 'cuda':
-        raise _lib.HPEError('prepare_input needs a ROCm GPU (MI355X / gfx950), got device %s' % (x.device,))
+        raise _lib.HPEError('%s needs a ROCm GPU (MI355X / gfx950), got device %s' % (what, x.device))
     n, h, w, _ = x.shape
     sn, sh, sw, sc = x.stride()
     if not (sc == 1 and sw == 3 and sh >= 3 * w and (n <= 1 or sn == h * sh)):
         x = x.contiguous()
         sh = 3 * w
-    x0, y0, cw, ch = crop_rect(h, w, crop)
+    return x, sh
+
+
+def _out_tensor(out, n, oh, ow, device):
     if out is None:
-        out = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=x.device)
-    elif (tuple(out.shape) != (n, oh, ow, 3) or out.dtype != torch.float32 or out.device != x.device
-          or not out.is_contiguous()):
-        raise ValueError('out must be a contiguous float32 (%d, %d, %d, 3) tensor on %s' % (n, oh, ow, x.device))
+        return torch.empty((n, oh, ow, 3), dtype=torch.float32, device=device)
+    if (tuple(out.shape) != (n, oh, ow, 3) or out.dtype != torch.float32 or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError('out must be a contiguous float32 (%d, %d, %d, 3) tensor on %s' % (n, oh, ow, device))
+    return out
+
+
+def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
+    """frames: uint8 (H, W, 3) or (n, H, W, 3), numpy array or tensor, host or device.  size: int or
+    (h, w) of the network input (128: front model, 256: back model).  bgr: the input is BGR (cv2
+    frames) and is reversed to RGB.  Returns the device tensor (n, h, w, 3) float32 (``out`` if given).
+    A device tensor whose pixels are contiguous is read in place through its row stride."""
+    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    x, sh = _device_frames(_checked_frames(frames, 'prepare_input'), device, out, 'prepare_input')
+    n, h, w, _ = x.shape
+    x0, y0, cw, ch = crop_rect(h, w, crop)
+    out = _out_tensor(out, n, oh, ow, x.device)
     lib = _lib.load()
     with torch.cuda.device(x.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.hpe_preprocess(ctypes.c_void_p(x.data_ptr()), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)),
                                       ctypes.c_void_p(out.data_ptr()), oh, ow, stream), 'hpe_preprocess')
+    return out
+
+
+def pad_bytes(pad_value):
+    """int or 3-tuple in the frame's channel order -> three ints in 0..255."""
+    p = (pad_value,) * 3 if np.isscalar(pad_value) else tuple(pad_value)
+    if len(p) != 3 or any(int(v) != v or not 0 <= int(v) <= 255 for v in p):
+        raise ValueError('pad_value must be an int or three ints in 0..255, got %r' % (pad_value,))
+    return tuple(int(v) for v in p)
+
+
+def roi_table(rois):
+    """(m, 5) int array-like or int32 tensor of (frame, x0, y0, w, h) rows -> the int32 tensor, where
+    it is."""
+    if torch.is_tensor(rois):
+        if rois.dtype != torch.int32:
+            raise ValueError('a rois tensor must be int32, got %s' % (rois.dtype,))
+        t = rois
+    else:
+        a = np.asarray(rois)
+        if a.size == 0:
+            a = a.reshape(-1, 5).astype(np.int32) if a.ndim < 2 else a.astype(np.int32)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('rois must be integers, got %s' % (a.dtype,))
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError('rois must fit int32')
+        t = torch.from_numpy(np.ascontiguousarray(a, np.int32))
+    if t.dim() != 2 or t.shape[1] != 5:
+        raise ValueError('rois must be (m, 5) rows of (frame, x0, y0, w, h), got %s' % (tuple(t.shape),))
+    return t
+
+
+def prepare_rois(frames, rois, size=128, bgr=True, pad_value=0, device=None, out=None):
+    """prepare_input per region of interest.  frames as prepare_input; rois: (m, 5) int array-like or
+    int32 device tensor, row r = (frame, x0, y0, w, h) in frame pixels, which may reach outside the
+    frame; pad_value: int or 3-tuple in the frame's channel order, the canvas outside the frame.
+    Returns the device tensor (m, h, w, 3) float32 (``out`` if given): row r is prepare_input of the
+    h x w canvas of ROI r.  An invalid row (frame outside 0..n-1, w or h outside 1..2^24, |x0| or |y0|
+    above 2^24) gives the prepared pad value."""
+    x = _checked_frames(frames, 'prepare_rois')
+    t = roi_table(rois)
+    p0, p1, p2 = pad_bytes(pad_value)
+    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    x, sh = _device_frames(x, device, out, 'prepare_rois')
+    t = t.to(x.device).contiguous()
+    n, h, w, _ = x.shape
+    m = t.shape[0]
+    out = _out_tensor(out, m, oh, ow, x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(lib.hpe_preprocess_rois(ctypes.c_void_p(x.data_ptr()), n, h, w, sh, ctypes.c_void_p(t.data_ptr()),
+                                           m, p0, p1, p2, int(bool(bgr)), ctypes.c_void_p(out.data_ptr()), oh, ow,
+                                           stream), 'hpe_preprocess_rois')
     return out

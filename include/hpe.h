@@ -252,6 +252,42 @@ int hpe_preprocess(const uint8_t *frames, int64_t n, int32_t in_h, int32_t in_w,
                    int32_t crop_x0, int32_t crop_y0, int32_t crop_w, int32_t crop_h, int32_t bgr,
                    float *out, int32_t out_h, int32_t out_w, void *stream);
 
+/* hpe_preprocess per region of interest: many rectangles per frame, each with its own frame, and
+ * rectangles that reach outside the frame (a second look at each face, frames placed on a larger
+ * canvas, batches whose frames need different crops).
+ * rois: device table (m, 5) int32, row r = (frame, x0, y0, w, h) in frame pixels.  Output r is exactly
+ * what hpe_preprocess produces for a whole h x w canvas whose pixel (y, x) is frames[frame, y0 + y,
+ * x0 + x] where that lies inside the frame and the bytes (pad_b0, pad_b1, pad_b2), in the frame's own
+ * channel order, elsewhere: the taps clamp to the canvas, not to the frame.  So an ROI inside the
+ * frame equals hpe_preprocess with that crop, and an ROI reaching outside equals hpe_preprocess on a
+ * host-padded copy, bit for bit.
+ * The table is on the device, so its rows are checked there: a row is valid iff 0 <= frame < n_frames,
+ * 1 <= w, h <= 2^24 and |x0|, |y0| <= 2^24 (every coordinate sum then fits int32).  An invalid row
+ * reads no frame memory; its output is the constant (lut[pad_c] - 0.5f) / 0.5f per channel, after the
+ * bgr swap.  Checked on the host (HPE_EINVAL): negative n_frames or m, non-positive sizes, a stride
+ * below 3 * in_w, pad bytes outside 0..255, m * out_h * out_w beyond int32, null pointers when m > 0
+ * (`frames` may be null when n_frames == 0: no row is valid then).  m == 0 is a no-op.
+ * out: (m, out_h, out_w, 3) fp32. */
+int hpe_preprocess_rois(const uint8_t *frames, int64_t n_frames, int32_t in_h, int32_t in_w,
+                        int64_t row_stride_bytes, const int32_t *rois, int64_t m, int32_t pad_b0,
+                        int32_t pad_b1, int32_t pad_b2, int32_t bgr, float *out, int32_t out_h, int32_t out_w,
+                        void *stream);
+
+/* hpe_detect's outputs -> the ROI table of a second detector pass (an enlarged square around every
+ * face), on the device.  count (n_images), boxes (n_images, max_faces, 4) as hpe_detect wrote them,
+ * normalised to the source rectangle (src_x0, src_y0, src_w, src_h) of the first pass in frame pixels.
+ * For frame i and detection j < count[i], in float64 with every operation rounded on its own:
+ *   px1 = src_x0 + x1 * src_w (likewise py1, px2, py2), cx = 0.5 * (px1 + px2), cy = 0.5 * (py1 + py2),
+ *   side = scale * max(px2 - px1, py2 - py1), S = clamp(ceil(side), 1, 2^24),
+ *   rx = floor(cx - 0.5 * S), ry = floor(cy - 0.5 * S), each clamped to +-2^24;
+ * the row is (i, rx, ry, S, S), or the invalid row (-1, 0, 0, 0, 0) if cx, cy or side is not finite.
+ * Rows are compacted frame-major in NMS order (offsets are a prefix sum over count, so the order is
+ * deterministic); n_rois[0] receives their number and the rows past it, up to n_images * max_faces,
+ * are (-1, 0, 0, 0, 0).  rois: (n_images * max_faces, 5) int32 — the table of hpe_preprocess_rois. */
+int hpe_face_rois(const int32_t *count, const double *boxes, int64_t n_images, int32_t max_faces,
+                  int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h, double scale, int32_t *rois,
+                  int32_t *n_rois, void *stream);
+
 const char *hpe_last_error(void);
 
 /* Build stamp: "src=<sha256/16 of the library's sources> git=<commit>[-dirty]" (csrc/Makefile).  The
