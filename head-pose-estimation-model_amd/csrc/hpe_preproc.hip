@@ -11,8 +11,11 @@
 // Every fp32 operation is rounded on its own: the file is compiled with contraction off, so no
 // multiply-add pair becomes an FMA (the only fused ops left are inside the division expansions).
 // One thread per output pixel (three channels), lanes along x; a gather bounded by load latency.
-// Below it: the same preparation per row of a device table of regions of interest that may reach
-// outside the frame (hpe_preprocess_rois), and the table of a second detector pass (hpe_face_rois).
+// Two kernels around one body: preprocess_kernel (one crop for the batch) and preprocess_rois_kernel
+// (one row of a device table of regions of interest per output, which may reach outside the frame)
+// differ in where the tap geometry comes from and in the gather; the table, the pixel decode, the row
+// load, the two filter passes and the store exist once.  Last: the table of a second detector pass
+// (hpe_face_rois).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,7 +29,7 @@
 
 typedef uint32_t u32u __attribute__((aligned(1)));   // a dword at any byte address
 
-struct PreArgs {
+struct PreArgs {           // filled by hpe_preprocess in this order, one line there per line here
   const uint8_t* frames;   // + crop origin of frame 0
   float* out;
   int64_t frame_stride, row_stride;   // bytes
@@ -74,50 +77,56 @@ __device__ __forceinline__ void taps(int o, float scale, int limit, int* idx, fl
   }
 }
 
-__global__ void __launch_bounds__(PRE_T) preprocess_kernel(PreArgs a) {
-  __shared__ float lut[256];   // byte -> (float)(byte / 255.0), the reference's float64 division
+// ---- the body preprocess_kernel and preprocess_rois_kernel share: everything but the gather ------
+// byte -> (float)(byte / 255.0), the reference's float64 division
+__device__ __forceinline__ void fill_lut(float* lut) {
   lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);
   __syncthreads();
+}
+
+// this thread's output pixel pix = (img * out_h + oy) * out_w + ox; false past the last one
+struct Px {
+  int pix, ox, oy;
+  int64_t img;
+};
+__device__ __forceinline__ bool decode_px(int total, int out_w, int out_h, Px* p) {
   const int64_t gid = (int64_t)blockIdx.x * PRE_T + threadIdx.x;
-  if (gid >= a.total) return;
-  const int pix = (int)gid;
-  const int ox = pix % a.out_w;
-  const int row = pix / a.out_w;
-  const int oy = row % a.out_h;
-  const int64_t img = row / a.out_h;
+  if (gid >= total) return false;
+  const int pix = (int)gid, row = pix / out_w;
+  *p = {pix, pix % out_w, row % out_h, row / out_h};
+  return true;
+}
 
-  int yi[4], xi[4];
-  float wy[4], wx[4];
-  taps(oy, a.sy, a.crop_h, yi, wy);
-  taps(ox, a.sx, a.crop_w, xi, wx);
-  // no x tap clamped: the four taps of a row are 12 contiguous bytes
-  const bool interior = xi[3] - xi[0] == 3;
-
-  const uint8_t* base = a.frames + img * a.frame_stride;
-  uint8_t b[4][12];
+// the four taps of one row where they are 12 contiguous bytes: three dword loads at any byte address
+__device__ __forceinline__ void load12(const uint8_t* p, uint8_t* b) {
+  const u32u* q = (const u32u*)p;
+  const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint8_t* r = base + (int64_t)yi[j] * a.row_stride;
-    if (interior) {
-      const u32u* q = (const u32u*)(r + xi[0] * 3);
-      const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        b[j][e] = (uint8_t)(q0 >> (8 * e));
-        b[j][4 + e] = (uint8_t)(q1 >> (8 * e));
-        b[j][8 + e] = (uint8_t)(q2 >> (8 * e));
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint8_t* p = r + xi[k] * 3;
-        b[j][3 * k] = p[0];
-        b[j][3 * k + 1] = p[1];
-        b[j][3 * k + 2] = p[2];
-      }
-    }
+  for (int e = 0; e < 4; ++e) {
+    b[e] = (uint8_t)(q0 >> (8 * e));
+    b[4 + e] = (uint8_t)(q1 >> (8 * e));
+    b[8 + e] = (uint8_t)(q2 >> (8 * e));
   }
-  // y pass: c[k][ch] = ((v0 wy0 + v1 wy1) + v2 wy2) + v3 wy3 for tap column k
+}
+
+// one tap: a pixel's three bytes
+__device__ __forceinline__ void load3(const uint8_t* p, uint8_t* b) {
+  b[0] = p[0];
+  b[1] = p[1];
+  b[2] = p[2];
+}
+
+// o: the three values in the frame's channel order
+__device__ __forceinline__ void store_px(float* dst, const float* o, int bgr) {
+  dst[0] = bgr ? o[2] : o[0];
+  dst[1] = o[1];
+  dst[2] = bgr ? o[0] : o[2];
+}
+
+// b[j][3 * k + ch]: the byte of tap row j, tap column k.  y pass: c[k][ch] = ((v0 wy0 + v1 wy1) + v2 wy2)
+// + v3 wy3 for tap column k; then the x pass over the four columns, (r - 0.5) / 0.5 and the store
+__device__ __forceinline__ void filter_store(const float* lut, const uint8_t (*b)[12], const float* wy,
+                                             const float* wx, int bgr, float* dst) {
   float c[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) {
@@ -131,61 +140,46 @@ __global__ void __launch_bounds__(PRE_T) preprocess_kernel(PreArgs a) {
     const float r = ((c[ch] * wx[0] + c[3 + ch] * wx[1]) + c[6 + ch] * wx[2]) + c[9 + ch] * wx[3];
     o[ch] = (r - 0.5f) / 0.5f;
   }
-  float* dst = a.out + (int64_t)pix * 3;
-  dst[0] = a.bgr ? o[2] : o[0];
-  dst[1] = o[1];
-  dst[2] = a.bgr ? o[0] : o[2];
+  store_px(dst, o, bgr);
 }
 
-extern "C" int hpe_preprocess(const uint8_t* frames, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
-                              int32_t crop_x0, int32_t crop_y0, int32_t crop_w, int32_t crop_h, int32_t bgr,
-                              float* out, int32_t out_h, int32_t out_w, void* stream) {
-  if (n < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess: negative frame count");
-  if (in_h <= 0 || in_w <= 0 || crop_w <= 0 || crop_h <= 0 || out_h <= 0 || out_w <= 0)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess: sizes must be positive (frame %d x %d, crop %d x %d, out %d x %d)",
-                    in_h, in_w, crop_h, crop_w, out_h, out_w);
-  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "hpe_preprocess: frame width %d too large", in_w);
-  if (crop_x0 < 0 || crop_y0 < 0 || (int64_t)crop_x0 + crop_w > in_w || (int64_t)crop_y0 + crop_h > in_h)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess: crop (%d, %d, %d, %d) outside the %d x %d frame", crop_x0, crop_y0,
-                    crop_w, crop_h, in_w, in_h);
-  if (row_stride_bytes < 3 * (int64_t)in_w)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess: row stride %lld below 3 * in_w = %lld", (long long)row_stride_bytes,
-                    3 * (long long)in_w);
-  if (row_stride_bytes > INT64_MAX / in_h || (n > 0 && row_stride_bytes * in_h > INT64_MAX / n))
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess: batch too large");
-  if (n > 0 && n > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess: n * out_h * out_w exceeds INT32_MAX");
-  if (n == 0) return HPE_OK;
-  if (!frames || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess: null argument");
-  PreArgs a;
-  a.frames = frames + (int64_t)crop_y0 * row_stride_bytes + (int64_t)crop_x0 * 3;
-  a.out = out;
-  a.frame_stride = (int64_t)in_h * row_stride_bytes;
-  a.row_stride = row_stride_bytes;
-  a.crop_w = crop_w;
-  a.crop_h = crop_h;
-  a.out_w = out_w;
-  a.out_h = out_h;
-  a.total = (int)(n * out_h * out_w);
-  a.bgr = bgr;
-  a.sx = (float)crop_w / (float)out_w;
-  a.sy = (float)crop_h / (float)out_h;
-  const unsigned grid = (unsigned)(((int64_t)a.total + PRE_T - 1) / PRE_T);
-  hipLaunchKernelGGL(preprocess_kernel, dim3(grid), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_preprocess launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+__global__ void __launch_bounds__(PRE_T) preprocess_kernel(PreArgs a) {
+  __shared__ float lut[256];
+  fill_lut(lut);
+  Px p;
+  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
+
+  int yi[4], xi[4];
+  float wy[4], wx[4];
+  taps(p.oy, a.sy, a.crop_h, yi, wy);
+  taps(p.ox, a.sx, a.crop_w, xi, wx);
+  // no x tap clamped: the four taps of a row are 12 contiguous bytes
+  const bool interior = xi[3] - xi[0] == 3;
+
+  const uint8_t* base = a.frames + p.img * a.frame_stride;
+  uint8_t b[4][12];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint8_t* r = base + (int64_t)yi[j] * a.row_stride;
+    if (interior) {
+      load12(r + xi[0] * 3, b[j]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) load3(r + xi[k] * 3, b[j] + 3 * k);
+    }
+  }
+  filter_store(lut, b, wy, wx, a.bgr, a.out + (int64_t)p.pix * 3);
 }
 
 // ---- per-row regions of interest ------------------------------------------------------------------
 // hpe_preprocess_rois: output r is hpe_preprocess of a whole h x w canvas whose pixel (y, x) is the
 // frame's pixel (y0 + y, x0 + x) where that lies inside the frame and the pad bytes elsewhere, for row
-// r = (frame, x0, y0, w, h) of a device table.  Same arithmetic in the same order as preprocess_kernel
+// r = (frame, x0, y0, w, h) of a device table.  The kernel is the shared body around its own gather
 // (taps clamp to the canvas, not to the frame), so an ROI inside the frame equals hpe_preprocess with
 // that crop and an ROI reaching outside equals hpe_preprocess on a host-padded copy, bit for bit.
 #define ROI_LIM (1 << 24)   // |x0|, |y0|, w, h <= 2^24: every coordinate sum below fits int32
 
-struct RoiArgs {
+struct RoiArgs {           // filled by hpe_preprocess_rois in this order, one line there per line here
   const uint8_t* frames;
   const int32_t* rois;     // (m, 5): frame, x0, y0, w, h
   float* out;
@@ -198,19 +192,13 @@ struct RoiArgs {
 
 __global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
   __shared__ float lut[256];
-  lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);
-  __syncthreads();
-  const int64_t gid = (int64_t)blockIdx.x * PRE_T + threadIdx.x;
-  if (gid >= a.total) return;
-  const int pix = (int)gid;
-  const int ox = pix % a.out_w;
-  const int row = pix / a.out_w;
-  const int oy = row % a.out_h;
-  const int64_t r = row / a.out_h;
+  fill_lut(lut);
+  Px p;   // p.img: the ROI row
+  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
 
-  const int32_t* roi = a.rois + r * 5;
+  const int32_t* roi = a.rois + p.img * 5;
   const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
-  float* dst = a.out + (int64_t)pix * 3;
+  float* dst = a.out + (int64_t)p.pix * 3;
   const uint8_t pad[3] = {(uint8_t)a.pad0, (uint8_t)a.pad1, (uint8_t)a.pad2};
   const bool valid = fr >= 0 && fr < a.n_frames && cw >= 1 && cw <= ROI_LIM && ch >= 1 && ch <= ROI_LIM &&
                      x0 >= -ROI_LIM && x0 <= ROI_LIM && y0 >= -ROI_LIM && y0 <= ROI_LIM;
@@ -218,16 +206,14 @@ __global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
     float o[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
-    dst[0] = a.bgr ? o[2] : o[0];
-    dst[1] = o[1];
-    dst[2] = a.bgr ? o[0] : o[2];
+    store_px(dst, o, a.bgr);
     return;
   }
 
   int yi[4], xi[4];
   float wy[4], wx[4];
-  taps(oy, (float)ch / (float)a.out_h, ch, yi, wy);
-  taps(ox, (float)cw / (float)a.out_w, cw, xi, wx);
+  taps(p.oy, (float)ch / (float)a.out_h, ch, yi, wy);
+  taps(p.ox, (float)cw / (float)a.out_w, cw, xi, wx);
   // frame coordinates of the taps (ascending along each axis, as the clamped canvas indices are)
   int fy[4], fx[4];
 #pragma unroll
@@ -244,51 +230,78 @@ __global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
   uint8_t b[4][12];
   if (interior) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const u32u* q = (const u32u*)(base + (int64_t)fy[j] * a.row_stride + fx[0] * 3);
-      const uint32_t q0 = q[0], q1 = q[1], q2 = q[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        b[j][e] = (uint8_t)(q0 >> (8 * e));
-        b[j][4 + e] = (uint8_t)(q1 >> (8 * e));
-        b[j][8 + e] = (uint8_t)(q2 >> (8 * e));
-      }
-    }
+    for (int j = 0; j < 4; ++j) load12(base + (int64_t)fy[j] * a.row_stride + fx[0] * 3, b[j]);
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool row_in = fy[j] >= 0 && fy[j] < a.in_h;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (row_in && fx[k] >= 0 && fx[k] < a.in_w) {
-          const uint8_t* p = base + (int64_t)fy[j] * a.row_stride + fx[k] * 3;
-          b[j][3 * k] = p[0];
-          b[j][3 * k + 1] = p[1];
-          b[j][3 * k + 2] = p[2];
-        } else {
-          b[j][3 * k] = pad[0];
-          b[j][3 * k + 1] = pad[1];
-          b[j][3 * k + 2] = pad[2];
-        }
+        if (row_in && fx[k] >= 0 && fx[k] < a.in_w)
+          load3(base + (int64_t)fy[j] * a.row_stride + fx[k] * 3, b[j] + 3 * k);
+        else
+          load3(pad, b[j] + 3 * k);
       }
     }
   }
-  float c[12];
-#pragma unroll
-  for (int e = 0; e < 12; ++e) {
-    c[e] = lut[b[0][e]] * wy[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j) c[e] = c[e] + lut[b[j][e]] * wy[j];
-  }
-  float o[3];
-#pragma unroll
-  for (int cc = 0; cc < 3; ++cc) {
-    const float v = ((c[cc] * wx[0] + c[3 + cc] * wx[1]) + c[6 + cc] * wx[2]) + c[9 + cc] * wx[3];
-    o[cc] = (v - 0.5f) / 0.5f;
-  }
-  dst[0] = a.bgr ? o[2] : o[0];
-  dst[1] = o[1];
-  dst[2] = a.bgr ? o[0] : o[2];
+  filter_store(lut, b, wy, wx, a.bgr, dst);
+}
+
+// what hpe_preprocess and hpe_preprocess_rois check of the frames and the output size, in the order
+// their callers see; crop: hpe_preprocess's (x0, y0, w, h), null for hpe_preprocess_rois
+static int check_frames(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
+                        const int32_t* crop, int32_t out_h, int32_t out_w) {
+  if (crop && (in_h <= 0 || in_w <= 0 || crop[2] <= 0 || crop[3] <= 0 || out_h <= 0 || out_w <= 0))
+    return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, crop %d x %d, out %d x %d)", fn, in_h,
+                    in_w, crop[3], crop[2], out_h, out_w);
+  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
+    return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, out %d x %d)", fn, in_h, in_w, out_h,
+                    out_w);
+  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "%s: frame width %d too large", fn, in_w);
+  if (crop && (crop[0] < 0 || crop[1] < 0 || (int64_t)crop[0] + crop[2] > in_w || (int64_t)crop[1] + crop[3] > in_h))
+    return hpe_fail(HPE_EINVAL, "%s: crop (%d, %d, %d, %d) outside the %d x %d frame", fn, crop[0], crop[1], crop[2],
+                    crop[3], in_w, in_h);
+  if (row_stride_bytes < 3 * (int64_t)in_w)
+    return hpe_fail(HPE_EINVAL, "%s: row stride %lld below 3 * in_w = %lld", fn, (long long)row_stride_bytes,
+                    3 * (long long)in_w);
+  if (row_stride_bytes > INT64_MAX / in_h || (n > 0 && row_stride_bytes * in_h > INT64_MAX / n))
+    return hpe_fail(HPE_EINVAL, "%s: batch too large", fn);
+  return HPE_OK;
+}
+
+// count (`what`: its name in the message) outputs of out_h x out_w pixels must fit the kernels' int index
+static int check_count(const char* fn, const char* what, int64_t count, int32_t out_h, int32_t out_w) {
+  if (count > 0 && count > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
+    return hpe_fail(HPE_EINVAL, "%s: %s * out_h * out_w exceeds INT32_MAX", fn, what);
+  return HPE_OK;
+}
+
+static unsigned pre_grid(int total) { return (unsigned)(((int64_t)total + PRE_T - 1) / PRE_T); }
+
+static int launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s launch: %s", fn, hipGetErrorString(e));
+  return HPE_OK;
+}
+
+extern "C" int hpe_preprocess(const uint8_t* frames, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
+                              int32_t crop_x0, int32_t crop_y0, int32_t crop_w, int32_t crop_h, int32_t bgr,
+                              float* out, int32_t out_h, int32_t out_w, void* stream) {
+  if (n < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess: negative frame count");
+  const int32_t crop[4] = {crop_x0, crop_y0, crop_w, crop_h};
+  if (int rc = check_frames("hpe_preprocess", n, in_h, in_w, row_stride_bytes, crop, out_h, out_w)) return rc;
+  if (int rc = check_count("hpe_preprocess", "n", n, out_h, out_w)) return rc;
+  if (n == 0) return HPE_OK;
+  if (!frames || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess: null argument");
+  const PreArgs a = {frames + (int64_t)crop_y0 * row_stride_bytes + (int64_t)crop_x0 * 3,
+                     out,
+                     (int64_t)in_h * row_stride_bytes, row_stride_bytes,
+                     crop_w, crop_h, out_w, out_h,
+                     (int)(n * out_h * out_w),
+                     bgr,
+                     (float)crop_w / (float)out_w, (float)crop_h / (float)out_h};
+  hipLaunchKernelGGL(preprocess_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
+  return launched("hpe_preprocess");
 }
 
 extern "C" int hpe_preprocess_rois(const uint8_t* frames, int64_t n_frames, int32_t in_h, int32_t in_w,
@@ -296,44 +309,25 @@ extern "C" int hpe_preprocess_rois(const uint8_t* frames, int64_t n_frames, int3
                                    int32_t pad_b1, int32_t pad_b2, int32_t bgr, float* out, int32_t out_h,
                                    int32_t out_w, void* stream) {
   if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: negative frame or ROI count");
-  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: sizes must be positive (frame %d x %d, out %d x %d)", in_h, in_w,
-                    out_h, out_w);
-  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: frame width %d too large", in_w);
-  if (row_stride_bytes < 3 * (int64_t)in_w)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: row stride %lld below 3 * in_w = %lld",
-                    (long long)row_stride_bytes, 3 * (long long)in_w);
-  if (n_frames > 0x7fffffff || row_stride_bytes > INT64_MAX / in_h ||
-      (n_frames > 0 && row_stride_bytes * in_h > INT64_MAX / n_frames))
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: batch too large");
+  if (int rc = check_frames("hpe_preprocess_rois", n_frames, in_h, in_w, row_stride_bytes, nullptr, out_h, out_w))
+    return rc;
+  if (n_frames > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: batch too large");
   if (pad_b0 < 0 || pad_b0 > 255 || pad_b1 < 0 || pad_b1 > 255 || pad_b2 < 0 || pad_b2 > 255)
     return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: pad bytes (%d, %d, %d) outside 0..255", pad_b0, pad_b1, pad_b2);
-  if (m > 0 && m > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: m * out_h * out_w exceeds INT32_MAX");
+  if (int rc = check_count("hpe_preprocess_rois", "m", m, out_h, out_w)) return rc;
   if (m == 0) return HPE_OK;
   // without frames every row is invalid and nothing is read through `frames`
   if ((!frames && n_frames > 0) || !rois || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: null argument");
-  RoiArgs a;
-  a.frames = frames;
-  a.rois = rois;
-  a.out = out;
-  a.frame_stride = (int64_t)in_h * row_stride_bytes;
-  a.row_stride = row_stride_bytes;
-  a.n_frames = (int)n_frames;
-  a.in_w = in_w;
-  a.in_h = in_h;
-  a.out_w = out_w;
-  a.out_h = out_h;
-  a.total = (int)(m * out_h * out_w);
-  a.bgr = bgr;
-  a.pad0 = pad_b0;
-  a.pad1 = pad_b1;
-  a.pad2 = pad_b2;
-  const unsigned grid = (unsigned)(((int64_t)a.total + PRE_T - 1) / PRE_T);
-  hipLaunchKernelGGL(preprocess_rois_kernel, dim3(grid), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_preprocess_rois launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  const RoiArgs a = {frames,
+                     rois,
+                     out,
+                     (int64_t)in_h * row_stride_bytes, row_stride_bytes,
+                     (int)n_frames, in_w, in_h, out_w, out_h,
+                     (int)(m * out_h * out_w),
+                     bgr,
+                     pad_b0, pad_b1, pad_b2};
+  hipLaunchKernelGGL(preprocess_rois_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
+  return launched("hpe_preprocess_rois");
 }
 
 // hpe_face_rois: hpe_detect's boxes -> the ROI table of a second pass.  One workgroup per frame: the
@@ -423,7 +417,5 @@ extern "C" int hpe_face_rois(const int32_t* count, const double* boxes, int64_t 
   hipLaunchKernelGGL(face_rois_kernel, dim3((unsigned)n_images), dim3(FROI_T), 0, (hipStream_t)stream, count, boxes,
                      (int)n_images, (int)max_faces, (double)src_x0, (double)src_y0, (double)src_w, (double)src_h,
                      scale, rois, n_rois);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_face_rois launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return launched("hpe_face_rois");
 }

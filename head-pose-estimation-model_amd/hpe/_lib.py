@@ -123,6 +123,17 @@ def load():
     return lib
 
 
+def ptr(t):
+    """Device pointer of a tensor (None -> null) as a ctypes argument."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def stream():
+    """torch's current stream as a ctypes argument."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def check(rc, what=''):
     if rc == 0:
         return

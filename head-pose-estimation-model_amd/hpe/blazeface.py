@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 
 BF_MAGIC = 0x46425048
 BFH_WORDS = 8
@@ -534,10 +535,6 @@ def build_plan(model_config, weights, stage=None, front=None):
 # ------------------------------------------------------------------------------------------------
 # device runner
 # ------------------------------------------------------------------------------------------------
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 class BlazeFace:
     """Batched forward of the unified BlazeFace + regressor graph.  ``predict(images)`` returns
     the unified model's outputs (Keras order) as numpy arrays; ``forward`` keeps them on device."""
@@ -608,9 +605,8 @@ class BlazeFace:
             taps.append(torch.empty(4, dtype=torch.float32, device=self.device))
         bufs = det + taps
         arr = (ctypes.c_void_p * 6)(*[b.data_ptr() for b in bufs])
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.hpe_blazeface_forward(self.h, _ptr(self.params), _ptr(x), n, arr, _ptr(self.ws),
-                                             stream), 'hpe_blazeface_forward')
+                                             _stream()), 'hpe_blazeface_forward')
         res = {o: det[i] for i, o in enumerate(self.plan['det_outs'])}
         for r, eng in self.regs:
             tap = taps[st['taps'].index(r['tap'])]

@@ -11,15 +11,15 @@ the frames (hpe_preprocess_rois) and ``detect_refine`` looks a second time at an
 every face of a first pass (hpe_face_rois); neither is in the reference.  ``EMAFilter`` is the webcam
 loop's pose smoothing (:16-35); webcam capture and drawing are out of scope.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 from .blazeface import BlazeFace
-from .preprocess import _checked_frames, _device_frames, crop_rect, prepare_input, prepare_rois
+from .preprocess import _checked_frames, _device_frames, _launch, crop_rect, prepare_input, prepare_rois
 
 KEY_POINT_SIZE = 6      # blazeFaceDetectorH5.py:8
 MAX_FACE_NUM = 100      # blazeFaceDetectorH5.py:9
@@ -67,8 +67,21 @@ def remap_roi(xy, rx, ry, side, src):
     return np.stack([(rx + xy[..., 0] * side - src[0]) / src[2], (ry + xy[..., 1] * side - src[1]) / src[3]], -1)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+def _device_input(frames, device):
+    """Prepared float frames, numpy array or tensor -> the contiguous float32 tensor on ``device``."""
+    x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
+    return x.to(device, torch.float32).contiguous()
+
+
+def _host_results(r, copy=False):
+    """r: postprocess()'s dict -> [Results] * n on the host; copy: for a caller that writes into them."""
+    h = {k: v.cpu().numpy() for k, v in r.items()}
+    res = []
+    for i, c in enumerate(int(c) for c in h['count']):
+        f = [h['boxes'][i, :c], h['keypoints'][i, :c], h['scores'][i, :c],
+             h['poses'][i, :c] if c else np.zeros((0, 3), np.float32)]
+        res.append(Results(*([a.copy() for a in f] if copy else f)))
+    return res
 
 
 class BlazeFaceDetector:
@@ -99,24 +112,16 @@ class BlazeFaceDetector:
         kps = torch.empty((n, M, KEY_POINT_SIZE, 2), dtype=torch.float64, device=dev)
         poses = torch.empty((n, M, 3), dtype=torch.float32, device=dev)
         lib = _lib.load()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         o = [x.contiguous() for x in outs]
         _lib.check(lib.hpe_detect(_ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), _ptr(o[4]), _ptr(o[5]), n,
                                   float(np.float32(self.sigmoidScoreThreshold)), float(self.iouThreshold), M,
                                   _ptr(count), _ptr(det), _ptr(scores), _ptr(boxes), _ptr(kps), _ptr(poses),
-                                  stream), 'hpe_detect')
+                                  _lib.stream()), 'hpe_detect')
         return dict(count=count, det_index=det, scores=scores, boxes=boxes, keypoints=kps, poses=poses)
 
     def _results(self, x):
         """x: (n, 128, 128, 3) device model input -> [Results] * n on the host."""
-        r = self.postprocess(self.net.forward(x))
-        h = {k: v.cpu().numpy() for k, v in r.items()}
-        res = []
-        for i in range(x.shape[0]):
-            c = int(h['count'][i])
-            res.append(Results(h['boxes'][i, :c], h['keypoints'][i, :c], h['scores'][i, :c],
-                               h['poses'][i, :c] if c else np.zeros((0, 3), np.float32)))
-        return res
+        return _host_results(self.postprocess(self.net.forward(x)))
 
     def prepare(self, images, bgr=True, crop=None):
         """uint8 frames (H, W, 3) / (n, H, W, 3) -> the device model input (hpe.preprocess)."""
@@ -133,8 +138,7 @@ class BlazeFaceDetector:
         (detect_images) -> [Results] * n."""
         if is_uint8(frames):
             return self.detect_images(frames)
-        x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
-        return self._results(x.to(self.device, torch.float32))
+        return self._results(_device_input(frames, self.device))
 
     def detect_rois(self, frames, rois, bgr=True, pad_value=0):
         """frames: raw uint8 frames; rois: (m, 5) rows of (frame, x0, y0, w, h) in frame pixels, which
@@ -152,12 +156,8 @@ class BlazeFaceDetector:
         n = r['count'].shape[0]
         rois = torch.empty((n * self.max_faces, 5), dtype=torch.int32, device=self.device)
         n_rois = torch.zeros(1, dtype=torch.int32, device=self.device)
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(lib.hpe_face_rois(_ptr(r['count']), _ptr(r['boxes']), n, self.max_faces, int(src[0]),
-                                         int(src[1]), int(src[2]), int(src[3]), float(scale), _ptr(rois),
-                                         _ptr(n_rois), stream), 'hpe_face_rois')
+        _launch('hpe_face_rois', self.device, _ptr(r['count']), _ptr(r['boxes']), n, self.max_faces, int(src[0]),
+                int(src[1]), int(src[2]), int(src[3]), float(scale), _ptr(rois), _ptr(n_rois))
         return rois, n_rois
 
     def detect_refine(self, frames, scale, bgr=True, crop=None, pad_value=0):
@@ -173,15 +173,12 @@ class BlazeFaceDetector:
         r = self.postprocess(self.net.forward(self.prepare(x, bgr=bgr, crop=crop)))
         rois, n_rois = self.face_rois(r, src, scale)
         m = int(n_rois.item())
-        h = {k: v.cpu().numpy() for k, v in r.items()}
+        res = _host_results(r, copy=True)
         second = self.detect_rois(x, rois[:m], bgr=bgr, pad_value=pad_value) if m else []
         table = rois[:m].cpu().numpy()
-        res, row = [], 0
-        for i in range(x.shape[0]):
-            c = int(h['count'][i])
-            out = Results(h['boxes'][i, :c].copy(), h['keypoints'][i, :c].copy(), h['scores'][i, :c].copy(),
-                          h['poses'][i, :c].copy() if c else np.zeros((0, 3), np.float32))
-            for j in range(c):
+        row = 0
+        for out in res:
+            for j in range(len(out.scores)):
                 fr, rx, ry, side, _ = (int(v) for v in table[row])
                 s2 = second[row]
                 row += 1
@@ -192,7 +189,6 @@ class BlazeFaceDetector:
                 out.boxes[j] = remap_roi(s2.boxes[0].reshape(2, 2), rx, ry, side, src).reshape(4)
                 out.keypoints[j] = remap_roi(s2.keypoints[0], rx, ry, side, src)
                 out.refined[j] = True
-            res.append(out)
         return res
 
     def detectFaces(self, frame):

@@ -12,17 +12,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .compiler import build_mirror, compile_graph
 
 OPT_KIND = {'sgd': 0, 'adam': 1, 'adamax': 2}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 _RCCL_COMMS = {}   # (group, device) -> the library's RCCL communicator for hpe_fit_steps_dp

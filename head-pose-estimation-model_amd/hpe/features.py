@@ -25,19 +25,25 @@ there.  That is the mechanism for the reference's ``*_Enlarged_features_*`` sets
 placed on a larger canvas; what the out-of-repo extractor did exactly (canvas size, pad colour) is
 unknown, so their recipe stays unpinned.  Features of an ROI pass are indexed by ROI row.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from .detector import BlazeFaceDetector, is_uint8
+from ._lib import ptr as _ptr
+from .detector import BlazeFaceDetector, _device_input, is_uint8
 from .preprocess import prepare_rois, roi_table
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+def _host_rois(rois, crop):
+    """extract's ``rois=``, array-like or tensor -> the checked host (m, 5) int32 array, which passes
+    through unchanged a second time; None stays None."""
+    if rois is None:
+        return None
+    if crop is not None:
+        raise ValueError('rois= takes no crop=')
+    return roi_table(rois.cpu() if torch.is_tensor(rois) else rois).numpy()
 
 
 class FeatureExtractor:
@@ -85,8 +91,7 @@ class FeatureExtractor:
         elif is_uint8(frames):
             x = self.det.prepare(frames, bgr=bgr, crop=crop)
         else:
-            x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
-            x = x.to(dev, torch.float32).contiguous()
+            x = _device_input(frames, dev)
         n = x.shape[0]
         r = self.det.postprocess(net.forward(x))
         k = self.max_faces
@@ -96,10 +101,9 @@ class FeatureExtractor:
         t0 = net.taps[self.tap_front].contiguous()
         t1 = net.taps[self.tap_back].contiguous()
         lib = _lib.load()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         _lib.check(lib.hpe_gather_features(_ptr(r['count']), _ptr(r['det_index']), n, self.max_faces, k,
                                            _ptr(t0), self.c_front, _ptr(t1), self.c_back, _ptr(f0), _ptr(f1),
-                                           _ptr(src), stream), 'hpe_gather_features')
+                                           _ptr(src), _lib.stream()), 'hpe_gather_features')
         r.update(feat88=f0, feat96=f1, src=src)
         return r
 
@@ -118,10 +122,7 @@ class FeatureExtractor:
         prepared on the device one ``batch_size`` slice at a time.  With ``rois`` (a host (m, 5) table,
         as extract_device) the slices are of ROI rows and the two index arrays are ROI rows."""
         fr, ir, bk, ib = [], [], [], []
-        if rois is not None:
-            if crop is not None:
-                raise ValueError('rois= takes no crop=')
-            rois = roi_table(rois.cpu() if torch.is_tensor(rois) else rois).numpy()
+        rois = _host_rois(rois, crop)
         n = len(frames) if rois is None else len(rois)
         for s in range(0, n, batch_size):
             if rois is None:
@@ -155,9 +156,10 @@ class FeatureExtractor:
         if len(poses) != len(frames):
             raise ValueError('need one (yaw, pitch, roll) per frame: %d frames, %d poses'
                              % (len(frames), len(poses)))
+        rois = _host_rois(rois, crop)
         f0, i0, f1, i1 = self.extract(frames, batch_size, bgr=bgr, crop=crop, rois=rois, pad_value=pad_value)
         if rois is not None:       # ROI rows -> frames; a detection in an invalid row's pad image has no pose
-            fr = roi_table(rois.cpu() if torch.is_tensor(rois) else rois).numpy()[:, 0]
+            fr = rois[:, 0]
             k0, k1 = ((fr[i] >= 0) & (fr[i] < len(frames)) for i in (i0, i1))
             f0, i0, f1, i1 = f0[k0], fr[i0][k0], f1[k1], fr[i1][k1]
         p0, p1 = self.dataset_names(prefix)

@@ -6,8 +6,6 @@ BlazePoser/blazeFaceDetectorH5.py:247-269 (cv2.COLOR_BGR2RGB, / 255.0, tf.image.
 uploaded as bytes; everything after the upload stays on the device.  Image decoding, webcam capture
 and drawing stay out of scope.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -67,21 +65,30 @@ def _out_tensor(out, n, oh, ow, device):
     return out
 
 
+def _out_hw(size):
+    """size: int or (h, w) of the network input -> (h, w)."""
+    return (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+
+
+def _launch(name, device, *args):
+    """Call the library's ``name(*args, stream)`` on ``device`` and its current stream and check it."""
+    fn = getattr(_lib.load(), name)
+    with torch.cuda.device(device):
+        _lib.check(fn(*args, _lib.stream()), name)
+
+
 def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
     """frames: uint8 (H, W, 3) or (n, H, W, 3), numpy array or tensor, host or device.  size: int or
     (h, w) of the network input (128: front model, 256: back model).  bgr: the input is BGR (cv2
     frames) and is reversed to RGB.  Returns the device tensor (n, h, w, 3) float32 (``out`` if given).
     A device tensor whose pixels are contiguous is read in place through its row stride."""
-    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    oh, ow = _out_hw(size)
     x, sh = _device_frames(_checked_frames(frames, 'prepare_input'), device, out, 'prepare_input')
     n, h, w, _ = x.shape
     x0, y0, cw, ch = crop_rect(h, w, crop)
     out = _out_tensor(out, n, oh, ow, x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.hpe_preprocess(ctypes.c_void_p(x.data_ptr()), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)),
-                                      ctypes.c_void_p(out.data_ptr()), oh, ow, stream), 'hpe_preprocess')
+    _launch('hpe_preprocess', x.device, _lib.ptr(x), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)), _lib.ptr(out), oh,
+            ow)
     return out
 
 
@@ -124,16 +131,12 @@ def prepare_rois(frames, rois, size=128, bgr=True, pad_value=0, device=None, out
     x = _checked_frames(frames, 'prepare_rois')
     t = roi_table(rois)
     p0, p1, p2 = pad_bytes(pad_value)
-    oh, ow = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    oh, ow = _out_hw(size)
     x, sh = _device_frames(x, device, out, 'prepare_rois')
     t = t.to(x.device).contiguous()
     n, h, w, _ = x.shape
     m = t.shape[0]
     out = _out_tensor(out, m, oh, ow, x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.hpe_preprocess_rois(ctypes.c_void_p(x.data_ptr()), n, h, w, sh, ctypes.c_void_p(t.data_ptr()),
-                                           m, p0, p1, p2, int(bool(bgr)), ctypes.c_void_p(out.data_ptr()), oh, ow,
-                                           stream), 'hpe_preprocess_rois')
+    _launch('hpe_preprocess_rois', x.device, _lib.ptr(x), n, h, w, sh, _lib.ptr(t), m, p0, p1, p2, int(bool(bgr)),
+            _lib.ptr(out), oh, ow)
     return out

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .compiler import ACTS, flatten_layers
 
 SPATIAL_OPS = ('GlobalAveragePooling2D', 'MultiHeadAttention')
@@ -33,16 +34,6 @@ SPATIAL_OPS = ('GlobalAveragePooling2D', 'MultiHeadAttention')
 def is_spatial(model_config):
     layers, _, _ = flatten_layers(model_config)
     return any(l['class_name'] in SPATIAL_OPS for l in layers)
-
-
-def _ptr(t):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    import ctypes
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _layer(cls, name, cfg, ins):

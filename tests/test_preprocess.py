@@ -211,9 +211,10 @@ def test_gpu_channel_order():
 @pytest.mark.gpu
 def test_gpu_offsets_past_4_gib():
     """342 frames of 2048 x 2048 x 3 bytes (4.3 GB): frame 341 starts past 2^31 and its lower tap
-    rows lie past 2^32 bytes."""
+    rows lie past 2^32 bytes.  The ROI kernel's frame and row address sums feed the same loads: two
+    full-frame rows give what the crop kernel gives."""
     import torch
-    from hpe.preprocess import prepare_input
+    from hpe.preprocess import prepare_input, prepare_rois
     n, s = 342, 2048
     if torch.cuda.mem_get_info()[0] < 6 * 1024 ** 3:
         pytest.skip('needs 6 GB of free device memory')
@@ -221,9 +222,11 @@ def test_gpu_offsets_past_4_gib():
     g = torch.Generator(device='cuda').manual_seed(7)
     dev = torch.randint(0, 256, (n, s, s, 3), dtype=torch.uint8, device='cuda', generator=g)
     got = prepare_input(dev, size=8)[[0, n - 1]].cpu().numpy()
+    rois = prepare_rois(dev, [(0, 0, 0, s, s), (n - 1, 0, 0, s, s)], size=8).cpu().numpy()
     ends = dev[[0, n - 1]].cpu().numpy()
     del dev
     np.testing.assert_array_equal(got, B.preprocess(ends, 8))
+    np.testing.assert_array_equal(rois, got)
 
 
 # ---- end to end: the uint8 entry points equal the float entry points -----------------------------
