@@ -11,7 +11,10 @@
 //                o_h = softmax(q_h k_h^T) v_h per head, q pre-scaled by 1/sqrt(key_dim)
 //                one workgroup per (image, head, 256 queries), one query per thread; keys / values
 //                of the head stream through LDS in blocks of 256 tokens; online softmax over
-//                32-key sub-blocks (one max + 32 exps per sub-block, fp32 throughout)
+//                32-key sub-blocks (one max + 32 exps per sub-block, fp32 throughout).
+//                Every 1 <= key_dim <= 64 runs: the kernels are instantiated at a few widths and a
+//                key_dim is rounded up to the next one (MFMA core, key_dim <= 32: the next even
+//                width; VALU core: 4, 8, 12, 16, 24, 32, 48, 64), the lanes past key_dim zero-filled
 //
 //   hpe_seg_mean per-image mean of rows: a terminal GlobalAveragePooling2D (Flatten-era graphs)
 //
@@ -108,7 +111,7 @@ __global__ void __launch_bounds__(SE_NT) seg_mean_kernel(const float* __restrict
 #define MHA_KB 256   // keys per LDS block
 #define MHA_SB 32    // keys per online-softmax sub-block
 
-// D: key_dim padded to a multiple of 4 (zero lanes past KD, the real key_dim)
+// D: key_dim rounded up to an instantiated width, a multiple of 4 (zero lanes past KD, the real key_dim)
 template <int D>
 __global__ void __launch_bounds__(MHA_QB) mha_kernel(const float* __restrict__ in, int ld_in, int C, int qoff,
                                                      const float* __restrict__ ps, int ld_ps,
@@ -339,6 +342,15 @@ extern "C" int hpe_seg_mean(const float* x, float* y, int64_t n_images, int32_t 
   return e == hipSuccess ? HPE_OK : hpe_fail(HPE_ERUNTIME, "hpe_seg_mean: %s", hipGetErrorString(e));
 }
 
+// the VALU kernel's instantiated widths; a key_dim between two of them runs at the next one up (the
+// kernel zero-fills lanes past the real key_dim, so the extra fmaf(q, 0, a) terms change nothing)
+static int mha_valu_width(int D) {
+  static const int W[] = {4, 8, 12, 16, 24, 32, 48, 64};
+  for (int w : W)
+    if (D <= w) return w;
+  return 0;
+}
+
 // in rows: q at float offset qoff, then k, v; pass-through rows ps (stride ld_ps) -> out[:, :C]
 static int mha_launch(const float* in, int32_t ld_in, int32_t qoff, const float* ps, int32_t ld_ps, int32_t C,
                       float* out, int32_t ld_out, int64_t n_images, int32_t P, int32_t H, int32_t D, void* stream) {
@@ -364,7 +376,7 @@ static int mha_launch(const float* in, int32_t ld_in, int32_t qoff, const float*
   if (grid > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_mha: grid too large");
 #define MHA_CASE(DD) \
   case DD: hipLaunchKernelGGL(mha_kernel<DD>, dim3((unsigned)grid), dim3(MHA_QB), 0, s, in, ld_in, C, qoff, ps, ld_ps, out, ld_out, P, H, nqb, D); break;
-  switch ((D + 3) & ~3) {
+  switch (mha_valu_width(D)) {
     MHA_CASE(4)
     MHA_CASE(8)
     MHA_CASE(12)
@@ -373,7 +385,7 @@ static int mha_launch(const float* in, int32_t ld_in, int32_t qoff, const float*
     MHA_CASE(32)
     MHA_CASE(48)
     MHA_CASE(64)
-    default: return hpe_fail(HPE_EINVAL, "hpe_mha: key_dim %d > 64 or unsupported", D);
+    default: return hpe_fail(HPE_EINVAL, "hpe_mha: key_dim %d > 64", D);
   }
 #undef MHA_CASE
   const hipError_t e = hipGetLastError();
@@ -383,7 +395,7 @@ static int mha_launch(const float* in, int32_t ld_in, int32_t qoff, const float*
 extern "C" int hpe_mha(const float* in, int32_t ld_in, int32_t C, float* out, int32_t ld_out,
                        int64_t n_images, int32_t P, int32_t H, int32_t D, void* stream) {
   if (!in || !out) return hpe_fail(HPE_EINVAL, "hpe_mha: null argument");
-  if (n_images < 0 || P <= 0 || C < 0 || H <= 0 || D <= 0 || ld_in < C + 3 * H * D || ld_out < C + H * D)
+  if (n_images < 0 || P <= 0 || C < 0 || H <= 0 || D <= 0 || D > 64 || ld_in < C + 3 * H * D || ld_out < C + H * D)
     return hpe_fail(HPE_EINVAL, "hpe_mha: bad shape P=%d C=%d H=%d D=%d ld_in=%d ld_out=%d", P, C, H, D,
                     ld_in, ld_out);
   return mha_launch(in, ld_in, C, in, ld_in, C, out, ld_out, n_images, P, H, D, stream);
@@ -392,7 +404,7 @@ extern "C" int hpe_mha(const float* in, int32_t ld_in, int32_t C, float* out, in
 extern "C" int hpe_mha_xg(const float* qkv, int32_t ld_qkv, const float* xg, int32_t C, float* out, int32_t ld_out,
                           int64_t n_images, int32_t P, int32_t H, int32_t D, void* stream) {
   if (!qkv || !out || (C > 0 && !xg)) return hpe_fail(HPE_EINVAL, "hpe_mha_xg: null argument");
-  if (n_images < 0 || P <= 0 || C < 0 || H <= 0 || D <= 0 || ld_qkv < 3 * H * D || ld_out < C + H * D)
+  if (n_images < 0 || P <= 0 || C < 0 || H <= 0 || D <= 0 || D > 64 || ld_qkv < 3 * H * D || ld_out < C + H * D)
     return hpe_fail(HPE_EINVAL, "hpe_mha_xg: bad shape P=%d C=%d H=%d D=%d ld_qkv=%d ld_out=%d", P, C, H, D,
                     ld_qkv, ld_out);
   return mha_launch(qkv, ld_qkv, 0, xg, C, C, out, ld_out, n_images, P, H, D, stream);

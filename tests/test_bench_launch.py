@@ -11,8 +11,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def test_launch_plan_is_pure_and_device_free():
+def _forbid_gpu_init(monkeypatch):
+    """The launcher must not initialise the GPU.  torch.cuda.is_initialized() shows that only while
+    nothing earlier in this process has used the GPU (a test module that sorts before this one may
+    have), so any initialisation attempt made meanwhile fails too.  Returns the state before."""
+    def boom(*a, **k):
+        raise AssertionError('launcher initialised the GPU')
+    monkeypatch.setattr(torch.cuda, '_lazy_init', boom)
+    monkeypatch.setattr(torch.cuda, 'init', boom)
+    return torch.cuda.is_initialized()
+
+
+def test_launch_plan_is_pure_and_device_free(monkeypatch):
     import bench
+    was = _forbid_gpu_init(monkeypatch)
     cmd = bench.launch_plan(4, ['--gpus', '4', '--steps', '5'], {})
     assert cmd[:3] == [sys.executable, '-m', 'torch.distributed.run']
     assert '--nproc-per-node' in cmd and cmd[cmd.index('--nproc-per-node') + 1] == '4'
@@ -22,7 +34,7 @@ def test_launch_plan_is_pure_and_device_free():
     # already a torchrun rank, or a single GPU: this process is the job
     assert bench.launch_plan(4, [], {'WORLD_SIZE': '4'}) is None
     assert bench.launch_plan(1, [], {}) is None
-    assert not torch.cuda.is_initialized()
+    assert torch.cuda.is_initialized() == was
 
 
 def test_gpus_2_without_gpus_fails_cleanly():
@@ -65,6 +77,7 @@ def test_visible_gpus_counts_without_hip(tmp_path, monkeypatch):
     """the launcher counts GPUs from KFD sysfs / the visible-devices env; torch's device
     count (which can initialise HIP in the parent) is never called."""
     import bench
+    was = _forbid_gpu_init(monkeypatch)
 
     def boom(*a, **k):
         raise AssertionError('launcher touched the HIP runtime')
@@ -85,7 +98,7 @@ def test_visible_gpus_counts_without_hip(tmp_path, monkeypatch):
     monkeypatch.setattr(bench, 'visible_gpus', lambda env=None, kfd=kfd: 8)
     assert bench.spawn_ranks(8, ['--gpus', '8']) == 0
     assert calls and calls[0][2] == 'torch.distributed.run'
-    assert not torch.cuda.is_initialized()
+    assert torch.cuda.is_initialized() == was
 
 
 @pytest.mark.gpu
