@@ -17,8 +17,18 @@
 // in MFMA operand order (one ds_read_b128 feeds four MFMAs, conflict-free); the residual Add of the
 // attention output is an add of xg in the epilogue, not an [I; Wo] GEMM; LayerNorm's row sums are an
 // in-lane sum plus two cross-lane steps.  HBM traffic per row: xg (C floats), o (H D floats), 3 out.
+//
+// Parameter buffer (hpe/spatial.py:_attn_tail; TD_NW floats, staged whole into LDS): the five kernels
+// Wo [HD][C], Wf1 [C][FF], Wf2 [FF][C], Wc1 [C][HID], Wc2 [HID][3], each as 16 x 16 tiles
+// [K/16][N/16][g][c][s] = W[16 bk + 4 g + s][16 bn + c], zero padded; then the nine vectors bo, g1,
+// be1, bf1, bf2, g2, be2, bc1, bc2, each zero padded to a 16-multiple, at the float offsets of the
+// descriptor words TD_BO..TD_BC2.  LayerNorm is over the first C features, with the biased variance
+// and eps inside the square root.  hpe_attn_tail_supported checks every descriptor word on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <cmath>
 
 #include "../../include/hpe.h"
 #include "hpe_common.h"
@@ -198,21 +208,45 @@ static tail_fn tail_pick(int cb, int hb, int fb, int nhb) {
 
 static int tail_blocks(int n) { return (n + 15) / 16; }
 
+// 1 when a kernel is compiled for the widths AND every word the kernel trusts is in range (all on
+// the host): the activation codes, the eps words (finite, positive), the nine vector offsets
+// (16-byte aligned, after the weight tiles, the padded vector inside the TD_NW staged floats) and
+// TD_NW itself (holds the tiles and the nine vectors, fits the LDS)
 extern "C" int hpe_attn_tail_supported(const int32_t* d) {
   if (!d) return 0;
-  if (d[TD_C] < 4 || d[TD_C] % 4 || d[TD_HD] < 4 || d[TD_HD] % 4) return 0;
+  if (d[TD_C] < 4 || d[TD_C] % 4 || d[TD_HD] < 4 || d[TD_HD] % 4 || d[TD_FF] < 1 || d[TD_HID] < 1) return 0;
+  if (d[TD_C] > 1024 || d[TD_HD] > 1024 || d[TD_FF] > 1024 || d[TD_HID] > 1024) return 0;   // n + 15 below
   const int cb = tail_blocks(d[TD_C]), hb = tail_blocks(d[TD_HD]), fb = tail_blocks(d[TD_FF]), nhb = tail_blocks(d[TD_HID]);
   if (!tail_pick(cb, hb, fb, nhb)) return 0;
-  return d[TD_NW] > 0 && (int64_t)d[TD_NW] * 4 <= 160 * 1024 && d[TD_NW] % 4 == 0;
+  for (int i = TD_ACT_FF; i <= TD_ACT_OUT; ++i)
+    if (d[i] < ACT_LINEAR || d[i] > ACT_LEAKY_RELU) return 0;
+  for (int i = TD_EPS1; i <= TD_EPS2; ++i) {
+    float eps;
+    memcpy(&eps, &d[i], sizeof eps);
+    if (!(eps > 0.f) || !std::isfinite(eps)) return 0;
+  }
+  const int64_t nw = d[TD_NW];
+  if (nw <= 0 || nw * 4 > 160 * 1024 || nw % 4) return 0;
+  const int64_t wend = 256 * (int64_t)(hb * cb + 2 * cb * fb + cb * nhb + nhb);
+  // padded lengths of bo, g1, be1, bf1, bf2, g2, be2, bc1, bc2 (the kernel reads whole 16-blocks)
+  const int len[9] = {16 * cb, 16 * cb, 16 * cb, 16 * fb, 16 * cb, 16 * cb, 16 * cb, 16 * nhb, 16};
+  int64_t need = wend;
+  for (int i = 0; i < 9; ++i) {
+    const int64_t off = d[TD_BO + i];
+    if (off < wend || off % 4 || off + len[i] > nw) return 0;
+    need += len[i];
+  }
+  return nw >= need;
 }
 
 extern "C" int hpe_attn_tail(const float* xg, int32_t ld_xg, const float* o, int32_t ld_o, int64_t n_rows,
                              const int32_t* desc, const float* w, float* y, void* stream) {
   if (!xg || !o || !desc || !w || !y) return hpe_fail(HPE_EINVAL, "hpe_attn_tail: null argument");
-  if (!hpe_attn_tail_supported(desc)) return hpe_fail(HPE_EINVAL, "hpe_attn_tail: unsupported geometry");
-  if (n_rows <= 0) return 0;
+  if (!hpe_attn_tail_supported(desc))
+    return hpe_fail(HPE_EINVAL, "hpe_attn_tail: unsupported geometry or bad descriptor");
   if (ld_xg < desc[TD_C] || ld_o < desc[TD_HD] || ld_xg % 4 || ld_o % 4)
     return hpe_fail(HPE_EINVAL, "hpe_attn_tail: bad strides %d %d", ld_xg, ld_o);
+  if (n_rows <= 0) return 0;
   TailArgs a = {};
   a.xg = xg; a.o = o; a.y = y; a.w = w; a.nrows = n_rows; a.ld_xg = ld_xg; a.ld_o = ld_o;
   for (int i = 0; i < TD_WORDS; ++i) a.d[i] = desc[i];

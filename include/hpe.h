@@ -355,7 +355,15 @@ int hpe_mha_xg(const float *qkv, int32_t ld_qkv, const float *xg, int32_t C, flo
  * writes y [n_rows][3].  desc: 20 host int32 words (C, H*D, ff_dim, hidden, activations, the two
  * LayerNorm epsilons as float bits, the parameter buffer's size and vector offsets); w: the device
  * parameter buffer hpe/spatial.py:_attn_tail prepares (weights in MFMA operand order, padded
- * vectors).  hpe_attn_tail_supported(desc): 1 when a kernel is compiled for these widths. */
+ * vectors; the layout is written out at the top of csrc/hpe_tail.hip).
+ * hpe_attn_tail_supported(desc), host only: 1 when a kernel is compiled for these widths (C in
+ * {84, 88, 92, 96}; H*D a multiple of 4 in 1, 2, 4 or 8 blocks of 16; (ff_dim, hidden) in (4, 8),
+ * (4, 4) or (2, 8) blocks of 16) and every other word is in range: the three activation codes in
+ * 0..9, both epsilons finite and positive, the buffer size a multiple of 4 floats that holds the
+ * weight tiles and the nine padded vectors and fits the 160 KB LDS, each vector offset a multiple
+ * of 4, at or after the end of the weight tiles, its padded vector inside the buffer.
+ * hpe_attn_tail returns HPE_EINVAL for a descriptor that hpe_attn_tail_supported refuses, for a
+ * null argument and for strides below the widths or not multiples of 4 (also when n_rows = 0). */
 int hpe_attn_tail_supported(const int32_t *desc);
 int hpe_attn_tail(const float *xg, int32_t ld_xg, const float *o, int32_t ld_o, int64_t n_rows,
                   const int32_t *desc, const float *w, float *y, void *stream);
