@@ -50,6 +50,8 @@ SIGNATURES = {
                                            _i32, _i32, _vp]),
     'hpe_face_rois': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, ctypes.c_double, _vp, _vp,
                                      _vp]),
+    'hpe_merge_rois': (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f,
+                                      _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'hpe_se_gate': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                    _vp]),
     'hpe_seg_mean': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

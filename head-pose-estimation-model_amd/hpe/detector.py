@@ -8,8 +8,10 @@ takes it (BGR): ``detect_images`` prepares it on the device (``prepareInputForIn
 RGB, /255, bicubic resize to 128x128, (x - 0.5) / 0.5 — hpe.preprocess, csrc/hpe_preproc.hip).  Float
 input is the already prepared model input.  ``detect_rois`` runs the detector on regions of interest of
 the frames (hpe_preprocess_rois) and ``detect_refine`` looks a second time at an enlarged square around
-every face of a first pass (hpe_face_rois); neither is in the reference.  ``EMAFilter`` is the webcam
-loop's pose smoothing (:16-35); webcam capture and drawing are out of scope.
+every face of a first pass (hpe_face_rois); ``detect_tiled`` looks at every frame as a whole and in
+overlapping tiles and merges the looks per frame on the device (hpe.preprocess.tile_rois,
+csrc/hpe_merge.hip, C ABI ``hpe_merge_rois``); none of the three is in the reference.  ``EMAFilter``
+is the webcam loop's pose smoothing (:16-35); webcam capture and drawing are out of scope.
 """
 import math
 
@@ -19,10 +21,12 @@ import torch
 from . import _lib
 from ._lib import ptr as _ptr
 from .blazeface import BlazeFace
-from .preprocess import _checked_frames, _device_frames, _launch, crop_rect, prepare_input, prepare_rois
+from .preprocess import (_checked_frames, _device_frames, _launch, crop_rect, prepare_input, prepare_rois,
+                         roi_table, tile_rois)
 
 KEY_POINT_SIZE = 6      # blazeFaceDetectorH5.py:8
 MAX_FACE_NUM = 100      # blazeFaceDetectorH5.py:9
+MERGE_MAX_CAND = 4096   # HPE_MERGE_MAX_CAND: rows per frame x max_faces that hpe_merge_rois takes
 
 
 class Results:
@@ -32,6 +36,10 @@ class Results:
         self.scores = scores
         self.poses = poses
         self.refined = np.zeros(len(scores), bool)   # detect_refine: the second pass replaced this face
+        # detect_tiled: the table row within the frame each face came from (0: the whole look when
+        # full) and its candidate index row * max_faces + slot among the frame's per-ROI detections
+        self.roi = np.zeros(len(scores), np.int32)
+        self.src = np.zeros(len(scores), np.int32)
 
 
 class EMAFilter:
@@ -189,6 +197,83 @@ class BlazeFaceDetector:
                 out.boxes[j] = remap_roi(s2.boxes[0].reshape(2, 2), rx, ry, side, src).reshape(4)
                 out.keypoints[j] = remap_roi(s2.keypoints[0], rx, ry, side, src)
                 out.refined[j] = True
+        return res
+
+    def merge_rois(self, r, rois, rows_per_frame, dst, max_faces=None):
+        """r: postprocess()'s dict for the ROI images of ``rois``, a frame-major (n * rows_per_frame, 5)
+        table (hpe.preprocess.tile_rois); dst: the rectangle (x0, y0, w, h) in frame pixels to normalise
+        to -> dict of device tensors count (n,), src, scores (n, max_faces), boxes, keypoints, poses:
+        per frame, all its rows' detections remapped to dst and merged by one NMS (hpe_merge_rois),
+        in selection order; src = row * max_faces_in + slot.  Slots past count are not written."""
+        R = int(rows_per_frame)
+        M = r['scores'].shape[1]
+        K = self.max_faces if max_faces is None else int(max_faces)
+        if R * M > MERGE_MAX_CAND:
+            raise ValueError('merge_rois: rows_per_frame %d x max_faces %d exceeds %d candidates per frame'
+                             % (R, M, MERGE_MAX_CAND))
+        t = roi_table(rois).to(self.device).contiguous()
+        if R < 1 or t.shape[0] % R or t.shape[0] != r['count'].shape[0]:
+            raise ValueError('merge_rois: %d table rows, %d ROI images, %d rows per frame'
+                             % (t.shape[0], r['count'].shape[0], R))
+        n = t.shape[0] // R
+        dev = self.device
+        out = dict(count=torch.zeros(n, dtype=torch.int32, device=dev),
+                   src=torch.empty((n, K), dtype=torch.int32, device=dev),
+                   scores=torch.empty((n, K), dtype=torch.float32, device=dev),
+                   boxes=torch.empty((n, K, 4), dtype=torch.float64, device=dev),
+                   keypoints=torch.empty((n, K, KEY_POINT_SIZE, 2), dtype=torch.float64, device=dev),
+                   poses=torch.empty((n, K, 3), dtype=torch.float32, device=dev))
+        _launch('hpe_merge_rois', dev, _ptr(t), n, R, _ptr(r['count']), _ptr(r['scores']), _ptr(r['boxes']),
+                _ptr(r['keypoints']), _ptr(r['poses']), M, int(dst[0]), int(dst[1]), int(dst[2]), int(dst[3]),
+                float(self.iouThreshold), K, _ptr(out['count']), _ptr(out['src']), _ptr(out['scores']),
+                _ptr(out['boxes']), _ptr(out['keypoints']), _ptr(out['poses']))
+        return out
+
+    def detect_tiled(self, frames, tile, overlap=None, full=True, bgr=True, crop=None, pad_value=0, max_faces=None,
+                     roi_batch=2048):
+        """Look at every frame as a whole (``full``: what detect_images(crop=) sees) and in square tiles
+        of ``tile`` frame pixels overlapping by ``overlap`` (None: tile // 4), and merge what all the
+        looks found: tile_rois -> prepare_rois -> the network -> postprocess -> merge_rois, with no host
+        read before the one copy of the merged results.  Returns one Results per frame, boxes and
+        keypoints normalised as detect_images(crop=) returns them, at most ``max_faces`` (None:
+        self.max_faces) per frame, with ``roi`` the table row each face came from (0: the whole look
+        when full) and ``src`` = row * self.max_faces + slot.  Batches of more than ``roi_batch`` ROI
+        images run in chunks of whole frames.  A mechanism, not a policy: a face cut by a tile border
+        gives a partial box that only the overlap and the whole look can outvote; no border rule is
+        applied and ``tile`` has no measured default."""
+        x = _checked_frames(frames, 'detect_tiled')
+        if x.ndim == 3:
+            x = x[None]
+        n, h, w, _ = x.shape
+        if overlap is None:
+            overlap = tile // 4 if tile is not None else 0
+        table, R = tile_rois(n, h, w, tile, overlap, crop=crop, full=full)
+        if R * self.max_faces > MERGE_MAX_CAND:
+            raise ValueError('detect_tiled: %d rows per frame x max_faces %d exceeds %d candidates per frame'
+                             % (R, self.max_faces, MERGE_MAX_CAND))
+        if int(roi_batch) < 1:
+            raise ValueError('detect_tiled: roi_batch must be positive, got %r' % (roi_batch,))
+        if n == 0:
+            return []
+        x, _ = _device_frames(x, self.device, None, 'detect_tiled')
+        dst = crop_rect(h, w, crop)
+        step = max(1, int(roi_batch) // R)          # whole frames per chunk
+        # a chunk's frames are numbered from 0, so every chunk reads the head of the one table
+        t = torch.from_numpy(table[:min(step, n) * R]).to(self.device)
+        parts = []
+        for f0 in range(0, n, step):
+            k = min(step, n - f0)
+            imgs = prepare_rois(x[f0:f0 + k], t[:k * R], size=tuple(self.net.structure['input_hw']), bgr=bgr,
+                                pad_value=pad_value, device=self.device)
+            parts.append(self.merge_rois(self.postprocess(self.net.forward(imgs)), t[:k * R], R, dst, max_faces))
+        m = {key: torch.cat([p[key] for p in parts]).cpu().numpy() for key in parts[0]}
+        res = []
+        for i, c in enumerate(int(c) for c in m['count']):
+            out = Results(m['boxes'][i, :c], m['keypoints'][i, :c], m['scores'][i, :c],
+                          m['poses'][i, :c] if c else np.zeros((0, 3), np.float32))
+            out.src = m['src'][i, :c]
+            out.roi = out.src // np.int32(self.max_faces)
+            res.append(out)
         return res
 
     def detectFaces(self, frame):

@@ -2,7 +2,8 @@
 BlazePoser/blazeFaceDetectorH5.py:247-269 (cv2.COLOR_BGR2RGB, / 255.0, tf.image.resize(method=
 'bicubic'), (x - 0.5) / 0.5) for a batch of uint8 frames in one kernel (csrc/hpe_preproc.hip, C ABI
 ``hpe_preprocess``), and the same per region of interest (``prepare_rois``, C ABI
-``hpe_preprocess_rois``): many rectangles per frame, which may reach outside it.  The frames are
+``hpe_preprocess_rois``): many rectangles per frame, which may reach outside it; ``tile_rois`` is the
+table of tiled detection (the whole look and overlapping square tiles of every frame).  The frames are
 uploaded as bytes; everything after the upload stays on the device.  Image decoding, webcam capture
 and drawing stay out of scope.
 """
@@ -119,6 +120,47 @@ def roi_table(rois):
     if t.dim() != 2 or t.shape[1] != 5:
         raise ValueError('rois must be (m, 5) rows of (frame, x0, y0, w, h), got %s' % (tuple(t.shape),))
     return t
+
+
+def tile_offsets(length, tile, overlap):
+    """Offsets of the tiles of side ``tile`` along an axis of ``length`` pixels, neighbours overlapping
+    by at least ``overlap``: the first starts at 0, the last ends at ``length``, every pixel is covered.
+    An axis no longer than the tile gets one centred tile (a negative offset: its outside is padded)."""
+    if length <= tile:
+        return [-((tile - length) // 2)]
+    step = tile - overlap
+    n = -(-(length - tile) // step) + 1
+    return [(i * (length - tile)) // (n - 1) for i in range(n)]
+
+
+def tile_rois(n_frames, h, w, tile, overlap, crop=None, full=True):
+    """The ROI table of tiled detection for ``n_frames`` frames of h x w: per frame, the rectangle
+    crop_rect(h, w, crop) that detect_images(crop=) looks at (row 0, if ``full``), then square tiles of
+    side ``tile`` over that rectangle, row-major (y outer, x inner), positioned by tile_offsets along
+    each axis.  tile=None: row 0 only.  Returns (rois (n_frames * R, 5) int32, R): frame-major, rows
+    f*R .. f*R+R-1 are frame f's, each (f, x0, y0, w, h) — the table of prepare_rois."""
+    sx, sy, sw, sh = crop_rect(h, w, crop)
+    if tile is None:
+        if not full:
+            raise ValueError('tile_rois: full=False with tile=None leaves no rows')
+        rows = []
+    else:
+        tile, overlap = int(tile), int(overlap)
+        if tile < 1:
+            raise ValueError('tile_rois: tile must be at least 1, got %d' % tile)
+        if not 0 <= overlap < tile:
+            raise ValueError('tile_rois: overlap must be in 0 .. tile - 1 = %d, got %d' % (tile - 1, overlap))
+        rows = [(sx + ox, sy + oy, tile, tile) for oy in tile_offsets(sh, tile, overlap)
+                for ox in tile_offsets(sw, tile, overlap)]
+    if full:
+        rows.insert(0, (sx, sy, sw, sh))
+    per_frame = np.asarray(rows, np.int64).reshape(len(rows), 4)
+    if np.abs(per_frame).max() >= 2 ** 31:
+        raise ValueError('tile_rois: rows must fit int32')
+    rois = np.empty((int(n_frames), len(rows), 5), np.int32)
+    rois[:, :, 0] = np.arange(int(n_frames), dtype=np.int32)[:, None]
+    rois[:, :, 1:] = per_frame.astype(np.int32)
+    return rois.reshape(-1, 5), len(rows)
 
 
 def prepare_rois(frames, rois, size=128, bgr=True, pad_value=0, device=None, out=None):

@@ -288,6 +288,39 @@ int hpe_face_rois(const int32_t *count, const double *boxes, int64_t n_images, i
                   int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h, double scale, int32_t *rois,
                   int32_t *n_rois, void *stream);
 
+/* Tiled detection's merge (csrc/hpe_merge.hip): the detections hpe_detect made on the ROI images of a
+ * frame-major table (hpe_preprocess_rois' `rois`, rows_per_frame = R rows per frame: rows f*R ..
+ * f*R+R-1 belong to frame f, e.g. the whole look and its tiles) brought back into the coordinates of
+ * one destination rectangle (dst_x0, dst_y0, dst_w, dst_h) in frame pixels, and the duplicates that
+ * overlapping rows produce removed by one NMS per frame.  One workgroup per frame.
+ * Inputs (device): count (n_frames*R), scores / boxes / keypoints / poses with M = max_faces_in slots per
+ * ROI image, as the detector post-processing wrote them.
+ * Candidates of frame f: (r, j) with r < R and j < min(max(count[f*R+r], 0), M), where row f*R+r passes
+ * the validity rule of hpe_preprocess_rois and its frame field is f; any other row contributes nothing,
+ * so (-1, 0, 0, 0, 0) is a legal filler.
+ * Remap, for row (f, rx, ry, rw, rh), in float64 with every operation rounded on its own and the ints
+ * converted exactly:
+ *   X = ((rx + x * rw) - dst_x0) / dst_w,  Y = ((ry + y * rh) - dst_y0) / dst_h
+ * for the two box corners and the six keypoints.  A candidate is dropped if a remapped box coordinate
+ * is not finite or its score is NaN.  Order: score descending, then r*M + j ascending.  NMS: that of
+ * the detector post-processing (greedy, IoU in fp32 on the fp32 casts of the remapped boxes, corner
+ * order agnostic, zero area gives IoU 0, suppress iff IoU > iou_threshold), at most max_faces_out kept.
+ * Outputs (device, per frame max_faces_out slots, the first count_out[f] valid, in selection order; the
+ * slots past it are not written): src_out int32 = r*M + j, scores_out / poses_out bit copies, boxes_out
+ * f64 [x1,y1,x2,y2] and keypoints_out f64 [6][2] remapped.
+ * Checked on the host (HPE_EINVAL): negative n_frames, non-positive rows_per_frame, max_faces_in,
+ * max_faces_out, dst_w or dst_h; |dst_x0|, |dst_y0|, dst_w or dst_h above 2^24; rows_per_frame *
+ * max_faces_in above HPE_MERGE_MAX_CAND (the workgroup's LDS: 64-bit sort keys, fp32 boxes and flags,
+ * 112 KB of the 160 KB at the cap); n_frames beyond int32; null pointers when n_frames > 0.
+ * n_frames == 0 is a no-op. */
+#define HPE_MERGE_MAX_CAND 4096
+int hpe_merge_rois(const int32_t *rois, int64_t n_frames, int32_t rows_per_frame, const int32_t *count,
+                   const float *scores, const double *boxes, const double *keypoints, const float *poses,
+                   int32_t max_faces_in, int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h,
+                   float iou_threshold, int32_t max_faces_out, int32_t *count_out, int32_t *src_out,
+                   float *scores_out, double *boxes_out, double *keypoints_out, float *poses_out,
+                   void *stream);
+
 const char *hpe_last_error(void);
 
 /* Build stamp: "src=<sha256/16 of the library's sources> git=<commit>[-dirty]" (csrc/Makefile).  The
