@@ -4,17 +4,31 @@
 //   extractDetections  anchor decode in fp64 (anchors: blazeFaceUtils.gen_anchors with the
 //                      detector's options: 16x16 x 2 + 8x8 x 6 centres, fixed size)        :284-317
 //   NMS                tf.image.non_max_suppression (V3): greedy by score (ties: lower index),
-//                      IoU in fp32 on the fp32-cast boxes, suppress iff IoU > threshold    :332
+//                      IoU in fp32 on the fp32-cast boxes, corner order agnostic, zero area ->
+//                      IoU 0, suppress iff IoU > threshold                                 :332
 //   pose gather        detection index -> pose cell of the 16x16 / 8x8 regressor map       :342-353
+// Every operation rounds on its own (contraction is off in this file, as in hpe_merge.hip): the IoU
+// is inter / ((area_i + area_j) - inter) with inter = h * w rounded to fp32 before it is subtracted,
+// as TensorFlow's kernel and oracle.detector_ref._iou have it.  A fused multiply-add in the
+// denominator moves the IoU by one ulp for about 8 % of overlapping pairs and flips the decision for
+// a pair whose IoU is the threshold.  The fp64 decode does not depend on the setting: its multiplies
+// (by 128, 0.5) are exact.
 // Candidates are compacted and bitonic-sorted in LDS (64-bit keys: ordered score, ~index); the
 // greedy pass suppresses in parallel across the workgroup, one barrier pair per kept box.
+// Non-finite loc values are not rejected and lie outside the parity claim: fminf / fmaxf return the
+// other operand for a NaN (Eigen's mini / maxi in TensorFlow's kernel depend on the operand order),
+// a NaN area fails area > 0 and gives IoU 0, and a NaN IoU never suppresses.  Such a frame's count
+// stays within [0, max_faces], its non-finite values are written through to boxes / keypoints, and
+// no other frame of the batch is affected.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/hpe.h"
 #include "hpe_common.h"
 
-#define DET_N0 512      // 16 x 16 cells x 2 anchors (stride 8)
+#pragma clang fp contract(off)
+
+#define DET_N0 512     // 16 x 16 cells x 2 anchors (stride 8)
 #define DET_N1 384      // 8 x 8 cells x 6 anchors (strides 16, 16, 16 merged)
 #define DET_N 896
 #define DET_SORT 1024
