@@ -52,6 +52,9 @@ SIGNATURES = {
                                      _vp]),
     'hpe_merge_rois': (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f,
                                       _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'hpe_track_reset': (ctypes.c_int, [_i64, _i32, _vp, _vp, _vp]),
+    'hpe_track': (ctypes.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_double, _f, _i32, _i32, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
     'hpe_se_gate': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                    _vp]),
     'hpe_seg_mean': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

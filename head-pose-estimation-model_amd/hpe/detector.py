@@ -11,7 +11,11 @@ the frames (hpe_preprocess_rois) and ``detect_refine`` looks a second time at an
 every face of a first pass (hpe_face_rois); ``detect_tiled`` looks at every frame as a whole and in
 overlapping tiles and merges the looks per frame on the device (hpe.preprocess.tile_rois,
 csrc/hpe_merge.hip, C ABI ``hpe_merge_rois``); none of the three is in the reference.  ``EMAFilter``
-is the webcam loop's pose smoothing (:16-35); webcam capture and drawing are out of scope.
+is the webcam loop's pose smoothing (:16-35), one scalar at a time on the host; ``detect_video`` does
+for a batch of video frames what that loop does per frame (:383-425: the 19 filters of a face's box,
+keypoints and angles) on the device, with the faces associated across frames first
+(hpe.tracking.PoseTracker, csrc/hpe_track.hip, C ABI ``hpe_track``).  Webcam capture and drawing are
+out of scope.
 """
 import math
 
@@ -40,6 +44,7 @@ class Results:
         # full) and its candidate index row * max_faces + slot among the frame's per-ROI detections
         self.roi = np.zeros(len(scores), np.int32)
         self.src = np.zeros(len(scores), np.int32)
+        self.track = np.full(len(scores), -1, np.int32)   # detect_video: the face's id across frames
 
 
 class EMAFilter:
@@ -275,6 +280,30 @@ class BlazeFaceDetector:
             out.roi = out.src // np.int32(self.max_faces)
             res.append(out)
         return res
+
+    def detect_video(self, frames, tracker, bgr=True, crop=None):
+        """frames: raw uint8 frames (T, H, W, 3), the next T frames of one video, or (S, T, H, W, 3), the
+        next T frames of each of tracker.streams = S videos; tracker: a hpe.tracking.PoseTracker, which
+        holds the tracks between calls, so consecutive calls continue the same videos.  prepare -> the
+        network -> postprocess -> tracker.update, one copy to the host at the end.  Returns T Results
+        (a list of S such lists for the 5-d form) as detect_images(bgr=, crop=) returns them, with
+        ``track`` the face's id (-1: untracked) and boxes, keypoints and poses smoothed per track."""
+        x = frames if torch.is_tensor(frames) else np.asarray(frames)
+        multi = x.ndim == 5
+        if x.ndim not in (4, 5):
+            raise ValueError('detect_video: frames must be (T, H, W, 3) or (S, T, H, W, 3), got %s' % (tuple(x.shape),))
+        S, T = (x.shape[0], x.shape[1]) if multi else (1, x.shape[0])
+        if S != tracker.streams:
+            raise ValueError('detect_video: %d videos for a tracker of %d streams' % (S, tracker.streams))
+        x = _checked_frames(x.reshape((S * T,) + tuple(x.shape[-3:])), 'detect_video')
+        if T == 0:
+            return [[] for _ in range(S)] if multi else []
+        r = tracker.update(self.postprocess(self.net.forward(self.prepare(x, bgr=bgr, crop=crop))))
+        track = r.pop('track').cpu().numpy()
+        res = _host_results(r)
+        for i, out in enumerate(res):
+            out.track = track[i, :len(out.scores)]
+        return [res[s * T:(s + 1) * T] for s in range(S)] if multi else res
 
     def detectFaces(self, frame):
         if is_uint8(frame):

@@ -321,6 +321,58 @@ int hpe_merge_rois(const int32_t *rois, int64_t n_frames, int32_t rows_per_frame
                    float *scores_out, double *boxes_out, double *keypoints_out, float *poses_out,
                    void *stream);
 
+/* Faces tracked across video frames and their box, keypoints and pose smoothed (csrc/hpe_track.hip):
+ * association by IoU and, per track, the webcam loop's 19 EMA filters (blazeFaceDetectorH5.py:16-35,
+ * :383-425: 4 box coordinates, 12 keypoint coordinates, 3 angles), which the reference indexes by a
+ * face's position in the frame's result list.  One workgroup per stream; no host read.
+ * Inputs (device): the detections of S = n_streams independent videos of T = n_frames consecutive
+ * frames each, stream-major (frame t of stream s is image g = s*T + t), M = max_faces slots per image
+ * as hpe_detect or hpe_merge_rois wrote them: count (S*T), boxes (S*T, M, 4) f64, keypoints
+ * (S*T, M, 6, 2) f64, poses (S*T, M, 3) f32.  Scores are not an input: the slot order within a frame
+ * (the NMS order) is the order the tracker takes the detections in.
+ * State (device, caller-owned, carried from call to call), K = max_tracks slots per stream:
+ *   state_i (S, 1 + 2K) int32, row s = [next_id, id_0 .. id_{K-1}, miss_0 .. miss_{K-1}]; an id below 0
+ *           is a free slot
+ *   state_d (S, K, HPE_TRACK_STATE_D) f64, per slot the smoothed box (4), keypoints (12) and pose (3),
+ *           then the slot's last matched raw box (4)
+ * hpe_track_reset writes next_id 0, every id -1, every miss 0 and every double 0.0.
+ * Per stream, for t = 0 .. T-1 in order: c = min(max(count[g], 0), M); every live track (id >= 0)
+ * starts the frame unmatched; for j = 0 .. c-1 in order, with m the detection's 19 values in float64
+ * (the pose floats convert exactly):
+ *   invalid  a box coordinate that is not finite: matches nothing, spawns nothing; track_out -1 and
+ *            the outputs are bit copies of the inputs
+ *   match    among the live tracks not yet matched in this frame, u = IoU of the detection's box and
+ *            the track's last raw box, both cast to fp32, by the detector's formula (corner order
+ *            agnostic, zero area gives 0, as hpe_merge_rois); a track qualifies iff u > match_iou; the
+ *            largest u wins, on a tie the lowest slot.  A negative match_iou lets a zero overlap match:
+ *            with one face that is the reference's position-only filter
+ *   update   on a match, each of the 19 values: state = alpha * m + (1.0 - alpha) * state in float64,
+ *            three separately rounded operations, 1.0 - alpha computed once (EMAFilter.update)
+ *   spawn    when nothing matches, the lowest free slot if there is one: id = next_id, next_id =
+ *            (next_id + 1) & 0x7fffffff, state = m (the first measurement passes through)
+ *   neither  no match and no free slot: track_out -1, outputs bit copies of the inputs
+ *   after a match or a spawn the slot is matched, its miss is 0 and its last raw box is the detection's
+ *   outputs  track_out (S*T, M) int32 the id; boxes_out, keypoints_out the slot's smoothed doubles;
+ *            poses_out (float) of the smoothed pose
+ * After the frame's detections every live unmatched track gets miss += 1 and is freed (id = -1) if
+ * miss > max_missed: reusable from the next frame on, never within the same frame.  A missed track's
+ * values are held, not extrapolated.  Output slots at or past c are not written, and no coasting
+ * tracks are emitted: the output has exactly the frame's detections.
+ * The outputs must not overlap the inputs or the state.  Nothing in the state is used as an index, so
+ * a corrupt state cannot cause an out-of-bounds access.
+ * Checked on the host (HPE_EINVAL, before any device call): negative n_streams or n_frames, max_faces
+ * < 1, max_tracks outside 1 .. HPE_TRACK_MAX_TRACKS, max_missed < 0, alpha outside (0, 1], a NaN
+ * match_iou, n_streams * n_frames beyond int32, null pointers when n_streams * n_frames > 0 (for
+ * hpe_track_reset: n_streams negative or beyond int32, max_tracks, null pointers when n_streams > 0).  n_streams * n_frames == 0 is a no-op that leaves the state
+ * untouched. */
+#define HPE_TRACK_MAX_TRACKS 64
+#define HPE_TRACK_STATE_D 23   /* doubles per track slot */
+int hpe_track_reset(int64_t n_streams, int32_t max_tracks, int32_t *state_i, double *state_d, void *stream);
+int hpe_track(int64_t n_streams, int32_t n_frames, int32_t max_faces, const int32_t *count,
+              const double *boxes, const double *keypoints, const float *poses, double alpha, float match_iou,
+              int32_t max_missed, int32_t max_tracks, int32_t *state_i, double *state_d, int32_t *track_out,
+              double *boxes_out, double *keypoints_out, float *poses_out, void *stream);
+
 const char *hpe_last_error(void);
 
 /* Build stamp: "src=<sha256/16 of the library's sources> git=<commit>[-dirty]" (csrc/Makefile).  The
