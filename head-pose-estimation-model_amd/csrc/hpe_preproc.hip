@@ -14,8 +14,10 @@
 // Two kernels around one body: preprocess_kernel (one crop for the batch) and preprocess_rois_kernel
 // (one row of a device table of regions of interest per output, which may reach outside the frame)
 // differ in where the tap geometry comes from and in the gather; the table, the pixel decode, the row
-// load, the two filter passes and the store exist once.  Last: the table of a second detector pass
-// (hpe_face_rois).
+// load, the two filter passes and the store exist once.  preprocess_nv12_kernel and
+// preprocess_rois_nv12_kernel are the same two around a gather that reads decoded NV12 video frames
+// and converts each tap to B, G, R bytes (hpe_preprocess_nv12, hpe_preprocess_rois_nv12).  Last: the
+// table of a second detector pass (hpe_face_rois).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -247,6 +249,226 @@ __global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
   filter_store(lut, b, wy, wx, a.bgr, dst);
 }
 
+// ---- NV12 frames ------------------------------------------------------------------------------------
+// hpe_preprocess_nv12 / hpe_preprocess_rois_nv12: the two kernels above with a gather that reads a
+// luma plane and a half-resolution plane of interleaved (U, V) pairs and fills b[][] with the B, G, R
+// bytes it converts per tap (include/hpe.h states the rule; tests/nv12_ref.py restates it), so the
+// output equals the BGR kernel's on the converted frame, bit for bit.  The chroma of pixel (y, x) is the
+// pair (y >> 1, x >> 1): a 4 x 4 window touches at most 3 chroma rows x 3 pairs.  The interior path
+// loads one dword of luma per tap row and each distinct pair once, all before the first conversion,
+// and computes a pair's three chroma terms once; no load touches a byte past in_w in a row.
+typedef uint16_t u16u __attribute__((aligned(1)));   // a (U, V) pair at any byte address
+
+#define NV12_SHIFT 20
+#define NV12_HALF (1 << (NV12_SHIFT - 1))
+
+struct Nv12Coef {
+  int cy, cvr, cvg, cug, cub;
+};
+__device__ __forceinline__ Nv12Coef nv12_coef(int matrix) {
+  if (matrix == 1) return {1220945, 1879825, -558796, -223607, 2215014};   // BT.709
+  return {1220542, 1673527, -852492, -409993, 2116026};                    // BT.601
+}
+
+struct Nv12Frame {   // one frame's two planes
+  const uint8_t *y, *uv;
+  int64_t y_row, uv_row;   // bytes
+};
+
+// what a (U, V) pair adds to the luma term of R, G and B, the rounding half included
+struct Chroma {
+  int r, g, b;
+};
+__device__ __forceinline__ Chroma chroma_terms(const Nv12Coef& k, int u, int v) {
+  u -= 128;
+  v -= 128;
+  return {k.cvr * v + NV12_HALF, k.cvg * v + k.cug * u + NV12_HALF, k.cub * u + NV12_HALF};
+}
+__device__ __forceinline__ Chroma pick(bool second, const Chroma& a, const Chroma& b) {
+  return {second ? b.r : a.r, second ? b.g : a.g, second ? b.b : a.b};
+}
+__device__ __forceinline__ uint8_t sat8(int v) { return (uint8_t)min(max(v, 0), 255); }
+
+// one pixel -> its three bytes in B, G, R order
+__device__ __forceinline__ void nv12_px(const Nv12Coef& k, int y, const Chroma& c, uint8_t* bgr) {
+  const int yy = max(y - 16, 0) * k.cy;
+  bgr[0] = sat8((yy + c.b) >> NV12_SHIFT);
+  bgr[1] = sat8((yy + c.g) >> NV12_SHIFT);
+  bgr[2] = sat8((yy + c.r) >> NV12_SHIFT);
+}
+
+// the window of tap rows fy[0..3] (ascending, steps of 0 or 1) and columns fx0 .. fx0 + 3, all inside
+// the frame.  Chroma rows: fy[0] >> 1 <= fy[1] >> 1, fy[2] >> 1 <= (fy[0] >> 1) + 1 and fy[3] >> 1, so
+// the three rows loaded are the first, the first + 1 (capped at the last) and the last.  Chroma pairs:
+// columns fx0 >> 1 and (fx0 >> 1) + 1 as one dword and (fx0 + 3) >> 1, the third pair for odd fx0
+// and the second again for even; the dword ends at byte 2 * (fx0 >> 1) + 3 <= in_w - 1.
+__device__ __forceinline__ void nv12_window(const Nv12Frame& f, const Nv12Coef& k, const int* fy, int fx0,
+                                            uint8_t (*b)[12]) {
+  const int cy0 = fy[0] >> 1, cy3 = fy[3] >> 1;
+  const int cr[3] = {cy0, min(cy0 + 1, cy3), cy3};
+  const int cx0 = fx0 >> 1, cx3 = (fx0 + 3) >> 1;
+  uint32_t yq[4], q01[3];
+  uint16_t q3[3];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) yq[j] = *(const u32u*)(f.y + (int64_t)fy[j] * f.y_row + fx0);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const uint8_t* r = f.uv + (int64_t)cr[s] * f.uv_row;
+    q01[s] = *(const u32u*)(r + 2 * cx0);
+    q3[s] = *(const u16u*)(r + 2 * cx3);
+  }
+  // c[s][kx]: chroma row slot s, tap column kx
+  const bool odd = fx0 & 1;
+  Chroma c[3][4];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    c[s][0] = chroma_terms(k, q01[s] & 255, (q01[s] >> 8) & 255);
+    c[s][2] = chroma_terms(k, (q01[s] >> 16) & 255, q01[s] >> 24);
+    c[s][3] = chroma_terms(k, q3[s] & 255, q3[s] >> 8);
+    c[s][1] = pick(odd, c[s][0], c[s][2]);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool up = (fy[j] >> 1) != cy0;   // rows 1 and 2: the first chroma row or the one after it
+#pragma unroll
+    for (int kx = 0; kx < 4; ++kx) {
+      const Chroma t = j == 0 ? c[0][kx] : j == 3 ? c[2][kx] : pick(up, c[0][kx], c[1][kx]);
+      nv12_px(k, (yq[j] >> (8 * kx)) & 255, t, b[j] + 3 * kx);
+    }
+  }
+}
+
+// the taps one by one (an x tap clamped, or part of the window outside the frame): in[j][kx] says
+// which taps lie in the frame; the others take the pad bytes as they are.  All loads first.
+__device__ __forceinline__ void nv12_taps(const Nv12Frame& f, const Nv12Coef& k, const int* fy, const int* fx,
+                                          const bool (*in)[4], const uint8_t* pad, uint8_t (*b)[12]) {
+  uint8_t yv[4][4], uu[4][4], vv[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int kx = 0; kx < 4; ++kx) {
+      yv[j][kx] = uu[j][kx] = vv[j][kx] = 0;
+      if (in[j][kx]) {
+        const uint8_t* c = f.uv + (int64_t)(fy[j] >> 1) * f.uv_row + 2 * (fx[kx] >> 1);
+        yv[j][kx] = f.y[(int64_t)fy[j] * f.y_row + fx[kx]];
+        uu[j][kx] = c[0];
+        vv[j][kx] = c[1];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int kx = 0; kx < 4; ++kx) {
+      if (in[j][kx])
+        nv12_px(k, yv[j][kx], chroma_terms(k, uu[j][kx], vv[j][kx]), b[j] + 3 * kx);
+      else
+        load3(pad, b[j] + 3 * kx);
+    }
+  }
+}
+
+struct PreNv12Args {       // filled by hpe_preprocess_nv12 in this order, one line there per line here
+  const uint8_t *y, *uv;   // frame 0
+  float* out;
+  int64_t y_frame, y_row, uv_frame, uv_row;   // bytes
+  int crop_x0, crop_y0, crop_w, crop_h, out_w, out_h;
+  int total;               // n * out_h * out_w
+  int matrix;
+  float sx, sy;            // (float)crop_w / (float)out_w, (float)crop_h / (float)out_h
+};
+
+__global__ void __launch_bounds__(PRE_T) preprocess_nv12_kernel(PreNv12Args a) {
+  __shared__ float lut[256];
+  fill_lut(lut);
+  Px p;
+  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
+
+  int yi[4], xi[4];
+  float wy[4], wx[4];
+  taps(p.oy, a.sy, a.crop_h, yi, wy);
+  taps(p.ox, a.sx, a.crop_w, xi, wx);
+  // frame coordinates: the chroma sample depends on their parity
+  int fy[4], fx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    fy[k] = a.crop_y0 + yi[k];
+    fx[k] = a.crop_x0 + xi[k];
+  }
+  const Nv12Coef coef = nv12_coef(a.matrix);
+  const Nv12Frame f = {a.y + p.img * a.y_frame, a.uv + p.img * a.uv_frame, a.y_row, a.uv_row};
+  uint8_t b[4][12];
+  if (xi[3] - xi[0] == 3) {   // no x tap clamped
+    nv12_window(f, coef, fy, fx[0], b);
+  } else {
+    const bool in[4][4] = {{true, true, true, true}, {true, true, true, true}, {true, true, true, true},
+                           {true, true, true, true}};
+    nv12_taps(f, coef, fy, fx, in, nullptr, b);
+  }
+  filter_store(lut, b, wy, wx, 1, a.out + (int64_t)p.pix * 3);
+}
+
+struct RoiNv12Args {       // filled by hpe_preprocess_rois_nv12 in this order, one line there per line here
+  const uint8_t *y, *uv;
+  const int32_t* rois;     // (m, 5): frame, x0, y0, w, h
+  float* out;
+  int64_t y_frame, y_row, uv_frame, uv_row;   // bytes
+  int n_frames, in_w, in_h, out_w, out_h;
+  int total;               // m * out_h * out_w
+  int matrix;
+  int pad_b, pad_g, pad_r;
+};
+
+__global__ void __launch_bounds__(PRE_T) preprocess_rois_nv12_kernel(RoiNv12Args a) {
+  __shared__ float lut[256];
+  fill_lut(lut);
+  Px p;   // p.img: the ROI row
+  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
+
+  const int32_t* roi = a.rois + p.img * 5;
+  const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
+  float* dst = a.out + (int64_t)p.pix * 3;
+  const uint8_t pad[3] = {(uint8_t)a.pad_b, (uint8_t)a.pad_g, (uint8_t)a.pad_r};
+  const bool valid = fr >= 0 && fr < a.n_frames && cw >= 1 && cw <= ROI_LIM && ch >= 1 && ch <= ROI_LIM &&
+                     x0 >= -ROI_LIM && x0 <= ROI_LIM && y0 >= -ROI_LIM && y0 <= ROI_LIM;
+  if (!valid) {   // reads no frame memory
+    float o[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
+    store_px(dst, o, 1);
+    return;
+  }
+
+  int yi[4], xi[4];
+  float wy[4], wx[4];
+  taps(p.oy, (float)ch / (float)a.out_h, ch, yi, wy);
+  taps(p.ox, (float)cw / (float)a.out_w, cw, xi, wx);
+  int fy[4], fx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    fy[k] = y0 + yi[k];
+    fx[k] = x0 + xi[k];
+  }
+  const bool x_in = fx[0] >= 0 && fx[3] < a.in_w;
+  const bool y_in = fy[0] >= 0 && fy[3] < a.in_h;
+  const Nv12Coef coef = nv12_coef(a.matrix);
+  const Nv12Frame f = {a.y + (int64_t)fr * a.y_frame, a.uv + (int64_t)fr * a.uv_frame, a.y_row, a.uv_row};
+  uint8_t b[4][12];
+  if (x_in && y_in && xi[3] - xi[0] == 3) {   // the whole window inside the frame and no x tap clamped
+    nv12_window(f, coef, fy, fx[0], b);
+  } else {
+    bool in[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool row_in = fy[j] >= 0 && fy[j] < a.in_h;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) in[j][k] = row_in && fx[k] >= 0 && fx[k] < a.in_w;
+    }
+    nv12_taps(f, coef, fy, fx, in, pad, b);
+  }
+  filter_store(lut, b, wy, wx, 1, dst);
+}
+
 // what hpe_preprocess and hpe_preprocess_rois check of the frames and the output size, in the order
 // their callers see; crop: hpe_preprocess's (x0, y0, w, h), null for hpe_preprocess_rois
 static int check_frames(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
@@ -265,6 +487,33 @@ static int check_frames(const char* fn, int64_t n, int32_t in_h, int32_t in_w, i
     return hpe_fail(HPE_EINVAL, "%s: row stride %lld below 3 * in_w = %lld", fn, (long long)row_stride_bytes,
                     3 * (long long)in_w);
   if (row_stride_bytes > INT64_MAX / in_h || (n > 0 && row_stride_bytes * in_h > INT64_MAX / n))
+    return hpe_fail(HPE_EINVAL, "%s: batch too large", fn);
+  return HPE_OK;
+}
+
+// the same for the NV12 entry points: two planes, each with a row and a frame stride in bytes
+static int check_nv12(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t y_row, int64_t y_frame,
+                      int64_t uv_row, int64_t uv_frame, int32_t matrix, const int32_t* crop, int32_t out_h,
+                      int32_t out_w) {
+  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
+    return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, out %d x %d)", fn, in_h, in_w, out_h,
+                    out_w);
+  if (crop && (crop[2] <= 0 || crop[3] <= 0))
+    return hpe_fail(HPE_EINVAL, "%s: crop sizes must be positive (%d x %d)", fn, crop[3], crop[2]);
+  if ((in_h | in_w) & 1) return hpe_fail(HPE_EINVAL, "%s: an NV12 frame's size %d x %d must be even", fn, in_h, in_w);
+  if (matrix != 0 && matrix != 1)
+    return hpe_fail(HPE_EINVAL, "%s: matrix %d is neither 0 (BT.601) nor 1 (BT.709)", fn, matrix);
+  if (crop && (crop[0] < 0 || crop[1] < 0 || (int64_t)crop[0] + crop[2] > in_w || (int64_t)crop[1] + crop[3] > in_h))
+    return hpe_fail(HPE_EINVAL, "%s: crop (%d, %d, %d, %d) outside the %d x %d frame", fn, crop[0], crop[1], crop[2],
+                    crop[3], in_w, in_h);
+  if (y_row < in_w || uv_row < in_w)
+    return hpe_fail(HPE_EINVAL, "%s: row strides (%lld, %lld) below in_w = %d", fn, (long long)y_row,
+                    (long long)uv_row, in_w);
+  if (y_frame < 0 || uv_frame < 0)
+    return hpe_fail(HPE_EINVAL, "%s: negative frame stride (%lld, %lld)", fn, (long long)y_frame, (long long)uv_frame);
+  // the last byte's offset, n * frame stride + in_h * row stride at most, must fit int64
+  const int64_t rows = y_row > uv_row ? y_row : uv_row, frames = y_frame > uv_frame ? y_frame : uv_frame;
+  if (rows > INT64_MAX / in_h || (n > 0 && frames > (INT64_MAX - rows * in_h) / n))
     return hpe_fail(HPE_EINVAL, "%s: batch too large", fn);
   return HPE_OK;
 }
@@ -328,6 +577,60 @@ extern "C" int hpe_preprocess_rois(const uint8_t* frames, int64_t n_frames, int3
                      pad_b0, pad_b1, pad_b2};
   hipLaunchKernelGGL(preprocess_rois_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
   return launched("hpe_preprocess_rois");
+}
+
+extern "C" int hpe_preprocess_nv12(const uint8_t* y, const uint8_t* uv, int64_t n, int32_t in_h, int32_t in_w,
+                                   int64_t y_row_stride, int64_t y_frame_stride, int64_t uv_row_stride,
+                                   int64_t uv_frame_stride, int32_t matrix, int32_t crop_x0, int32_t crop_y0,
+                                   int32_t crop_w, int32_t crop_h, float* out, int32_t out_h, int32_t out_w,
+                                   void* stream) {
+  if (n < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_nv12: negative frame count");
+  const int32_t crop[4] = {crop_x0, crop_y0, crop_w, crop_h};
+  if (int rc = check_nv12("hpe_preprocess_nv12", n, in_h, in_w, y_row_stride, y_frame_stride, uv_row_stride,
+                          uv_frame_stride, matrix, crop, out_h, out_w))
+    return rc;
+  if (int rc = check_count("hpe_preprocess_nv12", "n", n, out_h, out_w)) return rc;
+  if (n == 0) return HPE_OK;
+  if (!y || !uv || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess_nv12: null argument");
+  const PreNv12Args a = {y, uv,
+                         out,
+                         y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
+                         crop_x0, crop_y0, crop_w, crop_h, out_w, out_h,
+                         (int)(n * out_h * out_w),
+                         matrix,
+                         (float)crop_w / (float)out_w, (float)crop_h / (float)out_h};
+  hipLaunchKernelGGL(preprocess_nv12_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
+  return launched("hpe_preprocess_nv12");
+}
+
+extern "C" int hpe_preprocess_rois_nv12(const uint8_t* y, const uint8_t* uv, int64_t n_frames, int32_t in_h,
+                                        int32_t in_w, int64_t y_row_stride, int64_t y_frame_stride,
+                                        int64_t uv_row_stride, int64_t uv_frame_stride, const int32_t* rois,
+                                        int64_t m, int32_t pad_b, int32_t pad_g, int32_t pad_r, int32_t matrix,
+                                        float* out, int32_t out_h, int32_t out_w, void* stream) {
+  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: negative frame or ROI count");
+  if (int rc = check_nv12("hpe_preprocess_rois_nv12", n_frames, in_h, in_w, y_row_stride, y_frame_stride,
+                          uv_row_stride, uv_frame_stride, matrix, nullptr, out_h, out_w))
+    return rc;
+  if (n_frames > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: batch too large");
+  if (pad_b < 0 || pad_b > 255 || pad_g < 0 || pad_g > 255 || pad_r < 0 || pad_r > 255)
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: pad bytes (%d, %d, %d) outside 0..255", pad_b, pad_g,
+                    pad_r);
+  if (int rc = check_count("hpe_preprocess_rois_nv12", "m", m, out_h, out_w)) return rc;
+  if (m == 0) return HPE_OK;
+  // without frames every row is invalid and nothing is read through `y` or `uv`
+  if (((!y || !uv) && n_frames > 0) || !rois || !out)
+    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: null argument");
+  const RoiNv12Args a = {y, uv,
+                         rois,
+                         out,
+                         y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
+                         (int)n_frames, in_w, in_h, out_w, out_h,
+                         (int)(m * out_h * out_w),
+                         matrix,
+                         pad_b, pad_g, pad_r};
+  hipLaunchKernelGGL(preprocess_rois_nv12_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
+  return launched("hpe_preprocess_rois_nv12");
 }
 
 // hpe_face_rois: hpe_detect's boxes -> the ROI table of a second pass.  One workgroup per frame: the

@@ -48,6 +48,10 @@ SIGNATURES = {
                                       _i32, _vp]),
     'hpe_preprocess_rois': (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
                                            _i32, _i32, _vp]),
+    'hpe_preprocess_nv12': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
+                                           _i32, _i32, _vp, _i32, _i32, _vp]),
+    'hpe_preprocess_rois_nv12': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _i64, _i32,
+                                                _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     'hpe_face_rois': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, ctypes.c_double, _vp, _vp,
                                      _vp]),
     'hpe_merge_rois': (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f,

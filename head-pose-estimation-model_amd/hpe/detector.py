@@ -10,7 +10,8 @@ input is the already prepared model input.  ``detect_rois`` runs the detector on
 the frames (hpe_preprocess_rois) and ``detect_refine`` looks a second time at an enlarged square around
 every face of a first pass (hpe_face_rois); ``detect_tiled`` looks at every frame as a whole and in
 overlapping tiles and merges the looks per frame on the device (hpe.preprocess.tile_rois,
-csrc/hpe_merge.hip, C ABI ``hpe_merge_rois``); none of the three is in the reference.  ``EMAFilter``
+csrc/hpe_merge.hip, C ABI ``hpe_merge_rois``); none of the three is in the reference.  Wherever raw
+frames go, decoded NV12 video goes too, wrapped in hpe.preprocess.NV12Frames.  ``EMAFilter``
 is the webcam loop's pose smoothing (:16-35), one scalar at a time on the host; ``detect_video`` does
 for a batch of video frames what that loop does per frame (:383-425: the 19 filters of a face's box,
 keypoints and angles) on the device, with the faces associated across frames first
@@ -25,8 +26,8 @@ import torch
 from . import _lib
 from ._lib import ptr as _ptr
 from .blazeface import BlazeFace
-from .preprocess import (_checked_frames, _device_frames, _launch, crop_rect, prepare_input, prepare_rois,
-                         roi_table, tile_rois)
+from .preprocess import (NV12Frames, _checked_frames, _device_frames, _launch, crop_rect, frame_dims, prepare_input,
+                         prepare_rois, roi_table, tile_rois)
 
 KEY_POINT_SIZE = 6      # blazeFaceDetectorH5.py:8
 MAX_FACE_NUM = 100      # blazeFaceDetectorH5.py:9
@@ -67,7 +68,9 @@ class EMAFilter:
 
 
 def is_uint8(frames):
-    """Raw camera frames (uint8) as opposed to the prepared float model input."""
+    """Raw camera frames (uint8 BGR, or NV12Frames) as opposed to the prepared float model input."""
+    if isinstance(frames, NV12Frames):
+        return True
     if torch.is_tensor(frames):
         return frames.dtype == torch.uint8
     return isinstance(frames, np.ndarray) and frames.dtype == np.uint8
@@ -137,13 +140,16 @@ class BlazeFaceDetector:
         return _host_results(self.postprocess(self.net.forward(x)))
 
     def prepare(self, images, bgr=True, crop=None):
-        """uint8 frames (H, W, 3) / (n, H, W, 3) -> the device model input (hpe.preprocess)."""
+        """uint8 frames (H, W, 3) / (n, H, W, 3), or an NV12Frames -> the device model input
+        (hpe.preprocess)."""
         return prepare_input(images, size=tuple(self.net.structure['input_hw']), bgr=bgr, crop=crop,
                              device=self.device)
 
     def detect_images(self, images, bgr=True, crop=None):
         """images: raw uint8 frames (H, W, 3) or (n, H, W, 3), BGR unless bgr=False (numpy or
-        tensor, host or device); crop as hpe.preprocess.prepare_input -> [Results] * n."""
+        tensor, host or device); crop as hpe.preprocess.prepare_input -> [Results] * n.  Here and in
+        every method below that takes raw frames, an hpe.preprocess.NV12Frames (decoded video) stands
+        for the BGR frames it converts to; bgr=False is refused with one."""
         return self._results(self.prepare(images, bgr=bgr, crop=crop))
 
     def detect_batch(self, frames):
@@ -181,8 +187,9 @@ class BlazeFaceDetector:
         pass's order.  Where the second pass found anything in a face's ROI, its top-scoring detection
         replaces score, pose, box and keypoints (mapped back to the first pass's normalisation, in
         float64 on the host) and ``refined`` is True; otherwise the first-pass values stay."""
-        x, _ = _device_frames(_checked_frames(frames, 'detect_refine'), self.device, None, 'detect_refine')
-        src = crop_rect(x.shape[1], x.shape[2], crop)
+        x, _ = _device_frames(_checked_frames(frames, 'detect_refine', bgr), self.device, None, 'detect_refine')
+        _, h, w = frame_dims(x)
+        src = crop_rect(h, w, crop)
         r = self.postprocess(self.net.forward(self.prepare(x, bgr=bgr, crop=crop)))
         rois, n_rois = self.face_rois(r, src, scale)
         m = int(n_rois.item())
@@ -246,10 +253,10 @@ class BlazeFaceDetector:
         images run in chunks of whole frames.  A mechanism, not a policy: a face cut by a tile border
         gives a partial box that only the overlap and the whole look can outvote; no border rule is
         applied and ``tile`` has no measured default."""
-        x = _checked_frames(frames, 'detect_tiled')
-        if x.ndim == 3:
+        x = _checked_frames(frames, 'detect_tiled', bgr)
+        if not isinstance(x, NV12Frames) and x.ndim == 3:
             x = x[None]
-        n, h, w, _ = x.shape
+        n, h, w = frame_dims(x)
         if overlap is None:
             overlap = tile // 4 if tile is not None else 0
         table, R = tile_rois(n, h, w, tile, overlap, crop=crop, full=full)
@@ -283,19 +290,23 @@ class BlazeFaceDetector:
 
     def detect_video(self, frames, tracker, bgr=True, crop=None):
         """frames: raw uint8 frames (T, H, W, 3), the next T frames of one video, or (S, T, H, W, 3), the
-        next T frames of each of tracker.streams = S videos; tracker: a hpe.tracking.PoseTracker, which
+        next T frames of each of tracker.streams = S videos (an NV12Frames: y (T, H, W) or (S, T, H, W));
+        tracker: a hpe.tracking.PoseTracker, which
         holds the tracks between calls, so consecutive calls continue the same videos.  prepare -> the
         network -> postprocess -> tracker.update, one copy to the host at the end.  Returns T Results
         (a list of S such lists for the 5-d form) as detect_images(bgr=, crop=) returns them, with
         ``track`` the face's id (-1: untracked) and boxes, keypoints and poses smoothed per track."""
-        x = frames if torch.is_tensor(frames) else np.asarray(frames)
-        multi = x.ndim == 5
-        if x.ndim not in (4, 5):
-            raise ValueError('detect_video: frames must be (T, H, W, 3) or (S, T, H, W, 3), got %s' % (tuple(x.shape),))
-        S, T = (x.shape[0], x.shape[1]) if multi else (1, x.shape[0])
+        nv12 = isinstance(frames, NV12Frames)
+        x = frames if nv12 or torch.is_tensor(frames) else np.asarray(frames)
+        lead = x.lead if nv12 else tuple(x.shape[:-3])
+        multi = len(lead) == 2
+        if len(lead) not in (1, 2):
+            raise ValueError('detect_video: frames must be (T, H, W, 3) or (S, T, H, W, 3) (an NV12Frames: y (T, H, W) '
+                             'or (S, T, H, W)), got %s' % (tuple((x.y if nv12 else x).shape),))
+        S, T = (lead[0], lead[1]) if multi else (1, lead[0])
         if S != tracker.streams:
             raise ValueError('detect_video: %d videos for a tracker of %d streams' % (S, tracker.streams))
-        x = _checked_frames(x.reshape((S * T,) + tuple(x.shape[-3:])), 'detect_video')
+        x = _checked_frames(x.flat() if nv12 else x.reshape((S * T,) + tuple(x.shape[-3:])), 'detect_video', bgr)
         if T == 0:
             return [[] for _ in range(S)] if multi else []
         r = tracker.update(self.postprocess(self.net.forward(self.prepare(x, bgr=bgr, crop=crop))))

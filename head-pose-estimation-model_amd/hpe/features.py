@@ -77,8 +77,9 @@ class FeatureExtractor:
         return cls(m.model_config, m.weights_dict(), **kw)
 
     def extract_device(self, frames, bgr=True, crop=None, rois=None, pad_value=0):
-        """frames (n,128,128,3) prepared float input, or raw uint8 frames (n,H,W,3) (``bgr`` / ``crop``
-        as hpe.preprocess.prepare_input) -> dict of device tensors: feat88 (n,k,C0), feat96 (n,k,C1),
+        """frames (n,128,128,3) prepared float input, or raw uint8 frames (n,H,W,3) or an
+        hpe.preprocess.NV12Frames (``bgr`` / ``crop`` as hpe.preprocess.prepare_input) -> dict of
+        device tensors: feat88 (n,k,C0), feat96 (n,k,C1),
         src (n,k) int32 (0 front / 1 back / -1 none), plus the detector outputs.  With ``rois`` ((m, 5)
         rows of (frame, x0, y0, w, h), ``pad_value`` outside the frame: hpe.preprocess.prepare_rois)
         the inputs are the m regions of the uint8 frames and n = m."""

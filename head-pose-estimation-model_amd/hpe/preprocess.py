@@ -4,8 +4,12 @@ BlazePoser/blazeFaceDetectorH5.py:247-269 (cv2.COLOR_BGR2RGB, / 255.0, tf.image.
 ``hpe_preprocess``), and the same per region of interest (``prepare_rois``, C ABI
 ``hpe_preprocess_rois``): many rectangles per frame, which may reach outside it; ``tile_rois`` is the
 table of tiled detection (the whole look and overlapping square tiles of every frame).  The frames are
-uploaded as bytes; everything after the upload stays on the device.  Image decoding, webcam capture
-and drawing stay out of scope.
+uploaded as bytes; everything after the upload stays on the device.  Decoded video arrives as NV12 (a
+luma plane and a half-resolution plane of interleaved U, V): ``NV12Frames`` wraps such frames, and
+everything that takes uint8 BGR frames takes one and does what it would do for the frames converted to
+BGR by the fixed-point rule of include/hpe.h, the conversion happening inside the gather (C ABI
+``hpe_preprocess_nv12`` / ``hpe_preprocess_rois_nv12``).  Image decoding, webcam capture and drawing
+stay out of scope.
 """
 import numpy as np
 import torch
@@ -28,7 +32,89 @@ def crop_rect(h, w, crop):
     return tuple(int(c) for c in crop)
 
 
-def _checked_frames(frames, what):
+MATRICES = {'bt601': 0, 'bt709': 1}     # the `matrix` argument of hpe_preprocess_nv12
+
+
+def _u8_plane(x, name):
+    x = x if torch.is_tensor(x) else np.asarray(x)
+    if x.dtype != (torch.uint8 if torch.is_tensor(x) else np.uint8):
+        raise ValueError('NV12Frames takes uint8 planes, got %s for %s' % (x.dtype, name))
+    return x
+
+
+class NV12Frames:
+    """Decoded NV12 video frames: ``y`` uint8 (H, W) or (n, H, W) (for detect_video also (S, T, H, W)),
+    ``uv`` uint8 (..., H/2, W/2, 2) or (..., H/2, W) with the same leading axes, numpy arrays or
+    tensors, host or device; with ``uv=None``, ``y`` is the packed (..., 3H/2, W) layout (the Y rows,
+    then the UV rows).  The chroma of pixel (y, x) is uv[y >> 1][x >> 1]; ``matrix`` ('bt601' or
+    'bt709', both limited range) picks the coefficients of the conversion stated in include/hpe.h.
+    H and W must be even.  A device plane whose rows are contiguous is read in place through its
+    strides, so a decoder surface with a pitch above W, or two separate allocations, need no copy.
+    ``n``, ``h``, ``w``: the number of frames and the luma size; slicing along the first axis gives
+    an NV12Frames of the same planes."""
+
+    def __init__(self, y, uv=None, matrix='bt601'):
+        if matrix not in MATRICES:
+            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        y = _u8_plane(y, 'y')
+        if y.ndim not in (2, 3, 4):
+            raise ValueError('y must be (H, W), (n, H, W) or (S, T, H, W), got %s' % (tuple(y.shape),))
+        if uv is None:
+            rows = y.shape[-2]
+            if rows % 3:
+                raise ValueError('a packed NV12 frame has 3H/2 rows, got %d' % rows)
+            y, uv = y[..., :rows // 3 * 2, :], y[..., rows // 3 * 2:, :]
+        else:
+            uv = _u8_plane(uv, 'uv')
+        h, w = int(y.shape[-2]), int(y.shape[-1])
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError('an NV12 frame must have an even, positive size, got %d x %d' % (h, w))
+        lead = tuple(y.shape[:-2])
+        if uv.ndim == y.ndim + 1 and tuple(uv.shape) == lead + (h // 2, w // 2, 2):
+            uv = uv.reshape(lead + (h // 2, w))      # a view where the pairs are contiguous
+        if tuple(uv.shape) != lead + (h // 2, w):
+            raise ValueError('uv must be %s or %s for y %s, got %s' % (lead + (h // 2, w // 2, 2), lead + (h // 2, w),
+                                                                     tuple(y.shape), tuple(uv.shape)))
+        if not lead:
+            y, uv, lead = y[None], uv[None], (1,)
+        self.y, self.uv, self.matrix = y, uv, matrix
+        self.lead, self.h, self.w = lead, h, w
+        self.n = int(np.prod(lead))
+
+    def __len__(self):
+        return self.lead[0]
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice):
+            raise TypeError('NV12Frames takes slices along the frame axis, got %r' % (key,))
+        return NV12Frames(self.y[key], self.uv[key], self.matrix)
+
+    def flat(self):
+        """The same frames with one leading axis."""
+        if len(self.lead) == 1:
+            return self
+        return NV12Frames(self.y.reshape((self.n, self.h, self.w)), self.uv.reshape((self.n, self.h // 2, self.w)),
+                          self.matrix)
+
+    @property
+    def device(self):
+        return self.y.device if torch.is_tensor(self.y) else torch.device('cpu')
+
+
+def frame_dims(x):
+    """Checked frames (an NV12Frames, or a uint8 (H, W, 3) / (n, H, W, 3) array or tensor) -> (n, H, W)."""
+    if isinstance(x, NV12Frames):
+        return x.n, x.h, x.w
+    return (x.shape[0] if x.ndim == 4 else 1), x.shape[-3], x.shape[-2]
+
+
+def _checked_frames(frames, what, bgr=True):
+    if isinstance(frames, NV12Frames):
+        if not bgr:
+            raise ValueError('%s: bgr=False has no meaning for NV12Frames' % what)
+        if len(frames.lead) != 1:
+            raise ValueError('%s takes NV12Frames of (n, H, W), got y %s' % (what, tuple(frames.y.shape)))
+        return frames
     x = frames if torch.is_tensor(frames) else np.asarray(frames)
     if x.dtype != (torch.uint8 if torch.is_tensor(x) else np.uint8):
         raise ValueError('%s takes uint8 frames, got %s' % (what, x.dtype))
@@ -37,9 +123,30 @@ def _checked_frames(frames, what):
     return x
 
 
+def _device_plane(x, device, what):
+    """One plane (n, rows, W) of an NV12Frames -> the device tensor, read in place where its rows are
+    contiguous, and its (row, frame) strides in bytes."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    x = x.to(device)
+    if x.device.type != 'cuda':
+        raise _lib.HPEError('%s needs a ROCm GPU (MI355X / gfx950), got device %s' % (what, x.device))
+    if not (x.stride(2) == 1 and x.stride(1) >= x.shape[2]):
+        x = x.contiguous()
+    return x, (x.stride(1), x.stride(0))
+
+
 def _device_frames(x, device, out, what):
     """checked uint8 (H, W, 3) / (n, H, W, 3) frames -> (the (n, H, W, 3) device tensor, its row stride
-    in bytes).  A device tensor whose pixels are contiguous is read in place through its row stride."""
+    in bytes).  A device tensor whose pixels are contiguous is read in place through its row stride.
+    Checked NV12Frames -> (the NV12Frames of the two device planes, their (y row, y frame, uv row, uv
+    frame) strides in bytes)."""
+    if isinstance(x, NV12Frames):
+        if device is None:
+            device = next((p.device for p in (x.y, x.uv) if torch.is_tensor(p) and p.is_cuda),
+                          out.device if out is not None else 'cuda')
+        (y, sy), (uv, suv) = _device_plane(x.y, device, what), _device_plane(x.uv, device, what)
+        return NV12Frames(y, uv, x.matrix), sy + suv
     if not torch.is_tensor(x):
         x = torch.from_numpy(np.ascontiguousarray(x))
     if x.dim() == 3:
@@ -82,14 +189,19 @@ def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
     """frames: uint8 (H, W, 3) or (n, H, W, 3), numpy array or tensor, host or device.  size: int or
     (h, w) of the network input (128: front model, 256: back model).  bgr: the input is BGR (cv2
     frames) and is reversed to RGB.  Returns the device tensor (n, h, w, 3) float32 (``out`` if given).
-    A device tensor whose pixels are contiguous is read in place through its row stride."""
+    A device tensor whose pixels are contiguous is read in place through its row stride.  An NV12Frames
+    stands for the BGR frames it converts to (hpe_preprocess_nv12); bgr=False is refused with one."""
     oh, ow = _out_hw(size)
-    x, sh = _device_frames(_checked_frames(frames, 'prepare_input'), device, out, 'prepare_input')
-    n, h, w, _ = x.shape
+    x, sh = _device_frames(_checked_frames(frames, 'prepare_input', bgr), device, out, 'prepare_input')
+    n, h, w = frame_dims(x)
     x0, y0, cw, ch = crop_rect(h, w, crop)
     out = _out_tensor(out, n, oh, ow, x.device)
-    _launch('hpe_preprocess', x.device, _lib.ptr(x), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)), _lib.ptr(out), oh,
-            ow)
+    if isinstance(x, NV12Frames):
+        _launch('hpe_preprocess_nv12', x.device, _lib.ptr(x.y), _lib.ptr(x.uv), n, h, w, *sh, MATRICES[x.matrix],
+                x0, y0, cw, ch, _lib.ptr(out), oh, ow)
+    else:
+        _launch('hpe_preprocess', x.device, _lib.ptr(x), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)), _lib.ptr(out),
+                oh, ow)
     return out
 
 
@@ -169,16 +281,21 @@ def prepare_rois(frames, rois, size=128, bgr=True, pad_value=0, device=None, out
     frame; pad_value: int or 3-tuple in the frame's channel order, the canvas outside the frame.
     Returns the device tensor (m, h, w, 3) float32 (``out`` if given): row r is prepare_input of the
     h x w canvas of ROI r.  An invalid row (frame outside 0..n-1, w or h outside 1..2^24, |x0| or |y0|
-    above 2^24) gives the prepared pad value."""
-    x = _checked_frames(frames, 'prepare_rois')
+    above 2^24) gives the prepared pad value.  With an NV12Frames (hpe_preprocess_rois_nv12) the pad
+    bytes are B, G, R and are used as they are, not converted."""
+    x = _checked_frames(frames, 'prepare_rois', bgr)
     t = roi_table(rois)
     p0, p1, p2 = pad_bytes(pad_value)
     oh, ow = _out_hw(size)
     x, sh = _device_frames(x, device, out, 'prepare_rois')
     t = t.to(x.device).contiguous()
-    n, h, w, _ = x.shape
+    n, h, w = frame_dims(x)
     m = t.shape[0]
     out = _out_tensor(out, m, oh, ow, x.device)
-    _launch('hpe_preprocess_rois', x.device, _lib.ptr(x), n, h, w, sh, _lib.ptr(t), m, p0, p1, p2, int(bool(bgr)),
-            _lib.ptr(out), oh, ow)
+    if isinstance(x, NV12Frames):
+        _launch('hpe_preprocess_rois_nv12', x.device, _lib.ptr(x.y), _lib.ptr(x.uv), n, h, w, *sh, _lib.ptr(t), m,
+                p0, p1, p2, MATRICES[x.matrix], _lib.ptr(out), oh, ow)
+    else:
+        _launch('hpe_preprocess_rois', x.device, _lib.ptr(x), n, h, w, sh, _lib.ptr(t), m, p0, p1, p2,
+                int(bool(bgr)), _lib.ptr(out), oh, ow)
     return out

@@ -273,6 +273,50 @@ int hpe_preprocess_rois(const uint8_t *frames, int64_t n_frames, int32_t in_h, i
                         int32_t pad_b1, int32_t pad_b2, int32_t bgr, float *out, int32_t out_h, int32_t out_w,
                         void *stream);
 
+/* hpe_preprocess / hpe_preprocess_rois reading decoded NV12 video frames (what a hardware or software
+ * decoder and most cameras deliver) instead of packed BGR: the colour conversion happens per tap
+ * inside the gather, and everything after it is the BGR path with bgr = 1, so the output equals, bit
+ * for bit, hpe_preprocess(_rois) of the frame converted to BGR bytes by the rule below.
+ * Frame layout: y: n luma planes of in_h x in_w bytes, rows y_row_stride apart, frames y_frame_stride
+ * apart (bytes); uv: n chroma planes of in_h / 2 rows of in_w bytes (in_w / 2 interleaved U, V pairs),
+ * rows uv_row_stride apart, frames uv_frame_stride apart.  The planes may be separate allocations with
+ * their own pitch; the packed (3 in_h / 2, in_w) layout is uv = y + in_h * pitch.  in_h and in_w must
+ * be even.  The chroma of pixel (y, x) is the pair uv[y >> 1][x >> 1] (the nearest sample, shared by
+ * the four pixels of a 2 x 2 block; no chroma interpolation).  No byte outside [row start, row start
+ * + in_w) of either plane is read.
+ * Conversion, int32, OpenCV's fixed-point form with a shift of 20 (limited range in, full range out):
+ *   yy = max(Y - 16, 0) * CY,  u = U - 128,  v = V - 128
+ *   R = sat8((yy + CVR * v           + (1 << 19)) >> 20)
+ *   G = sat8((yy + CVG * v + CUG * u + (1 << 19)) >> 20)
+ *   B = sat8((yy + CUB * u           + (1 << 19)) >> 20)
+ * with >> an arithmetic shift (a floor for negative sums) and sat8 a clamp to 0..255; the sums stay
+ * below 2^31 for every (Y, U, V).  matrix picks the coefficients (CY, CVR, CVG, CUG, CUB):
+ *   0, BT.601: 1220542, 1673527, -852492, -409993, 2116026 (the constants of OpenCV's
+ *              COLOR_YUV2BGR_NV12)
+ *   1, BT.709: 1220945, 1879825, -558796, -223607, 2215014 (round(c * 2^20) of the exact BT.709
+ *              limited-range matrix)
+ * tests/nv12_ref.py restates the rule.  out is RGB, as from hpe_preprocess with bgr = 1.
+ * Checked on the host (HPE_EINVAL) before any device call: a negative n, non-positive or odd in_h /
+ * in_w, non-positive crop or output sizes, a crop outside the frame, row strides below in_w, negative
+ * frame strides, matrix outside 0..1, counts and strides that overflow, null pointers when n > 0.
+ * n == 0 is a no-op. */
+int hpe_preprocess_nv12(const uint8_t *y, const uint8_t *uv, int64_t n, int32_t in_h, int32_t in_w,
+                        int64_t y_row_stride, int64_t y_frame_stride, int64_t uv_row_stride,
+                        int64_t uv_frame_stride, int32_t matrix, int32_t crop_x0, int32_t crop_y0,
+                        int32_t crop_w, int32_t crop_h, float *out, int32_t out_h, int32_t out_w, void *stream);
+
+/* hpe_preprocess_rois on NV12 frames (described as for hpe_preprocess_nv12): the table, the validity
+ * rule, the frame-or-pad decision per tap and the invalid row's output are those of
+ * hpe_preprocess_rois with bgr = 1.  The pad bytes are given as B, G, R and used as they are, not
+ * converted.  Also checked on the host: pad bytes outside 0..255, a negative m, m * out_h * out_w
+ * beyond int32, null pointers when m > 0 (`y` and `uv` may be null when n_frames == 0).  m == 0 is a
+ * no-op. */
+int hpe_preprocess_rois_nv12(const uint8_t *y, const uint8_t *uv, int64_t n_frames, int32_t in_h, int32_t in_w,
+                             int64_t y_row_stride, int64_t y_frame_stride, int64_t uv_row_stride,
+                             int64_t uv_frame_stride, const int32_t *rois, int64_t m, int32_t pad_b,
+                             int32_t pad_g, int32_t pad_r, int32_t matrix, float *out, int32_t out_h,
+                             int32_t out_w, void *stream);
+
 /* hpe_detect's outputs -> the ROI table of a second detector pass (an enlarged square around every
  * face), on the device.  count (n_images), boxes (n_images, max_faces, 4) as hpe_detect wrote them,
  * normalised to the source rectangle (src_x0, src_y0, src_w, src_h) of the first pass in frame pixels.
