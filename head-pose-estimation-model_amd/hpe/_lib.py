@@ -59,6 +59,11 @@ SIGNATURES = {
     'hpe_track_reset': (ctypes.c_int, [_i64, _i32, _vp, _vp, _vp]),
     'hpe_track': (ctypes.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_double, _f, _i32, _i32, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp]),
+    'hpe_draw': (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
+    'hpe_draw_nv12': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _i32,
+                                     _vp]),
+    'hpe_pose_prims': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                      _i32, _vp, _vp, _vp]),
     'hpe_se_gate': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                    _vp]),
     'hpe_seg_mean': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),

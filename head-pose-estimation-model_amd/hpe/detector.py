@@ -15,8 +15,10 @@ frames go, decoded NV12 video goes too, wrapped in hpe.preprocess.NV12Frames.  `
 is the webcam loop's pose smoothing (:16-35), one scalar at a time on the host; ``detect_video`` does
 for a batch of video frames what that loop does per frame (:383-425: the 19 filters of a face's box,
 keypoints and angles) on the device, with the faces associated across frames first
-(hpe.tracking.PoseTracker, csrc/hpe_track.hip, C ABI ``hpe_track``).  Webcam capture and drawing are
-out of scope.
+(hpe.tracking.PoseTracker, csrc/hpe_track.hip, C ABI ``hpe_track``).  ``draw`` is the loop's last stage,
+``drawDetections`` (:175-219: box, keypoints and pose axes, without the text), on the device and in place
+for device frames (hpe.draw, csrc/hpe_draw.hip, C ABI ``hpe_pose_prims`` / ``hpe_draw`` / ``hpe_draw_nv12``).
+Webcam capture is out of scope.
 """
 import math
 
@@ -26,6 +28,7 @@ import torch
 from . import _lib
 from ._lib import ptr as _ptr
 from .blazeface import BlazeFace
+from .draw import DrawStyle, draw_prims, pack_results, pose_prims
 from .preprocess import (NV12Frames, _checked_frames, _device_frames, _launch, crop_rect, frame_dims, prepare_input,
                          prepare_rois, roi_table, tile_rois)
 
@@ -315,6 +318,45 @@ class BlazeFaceDetector:
         for i, out in enumerate(res):
             out.track = track[i, :len(out.scores)]
         return [res[s * T:(s + 1) * T] for s in range(S)] if multi else res
+
+    def draw(self, frames, results, bgr=True, crop=None, style=None):
+        """Draw every face's box, keypoints and pose axes into the frames (the reference's drawDetections,
+        :175-219, without its text).  frames: raw uint8 frames (H, W, 3) / (n, H, W, 3), BGR unless
+        bgr=False, or an NV12Frames.  results: the device dict of postprocess, merge_rois or
+        PoseTracker.update for the n frames (nothing is read on the host), or the list of host Results a
+        detect_* method returned (packed and uploaded).  crop: as in detect_images, the rectangle the
+        detections are normalised to.  style: a hpe.draw.DrawStyle (None: the reference's sizes and
+        colours; for NV12 the colours are converted to Y, U, V by hpe.draw.bgr_to_yuv).  Device frames
+        are annotated in place and returned; host frames are copied to the device, annotated and
+        returned as a new array of the same kind (an NV12Frames gives an NV12Frames)."""
+        style = DrawStyle() if style is None else style
+        x = _checked_frames(frames, 'draw', bgr)
+        nv12 = isinstance(x, NV12Frames)
+        on_device = all(torch.is_tensor(p) and p.is_cuda for p in ((x.y, x.uv) if nv12 else (x,)))
+        d = x if on_device else _device_frames(x, self.device, None, 'draw')[0]
+        n, h, w = frame_dims(d)
+        if isinstance(results, dict):
+            r = results
+        else:
+            res = [results] if isinstance(results, Results) else list(results)
+            r = {k: torch.from_numpy(v).to(self.device) for k, v in pack_results(res).items()}
+        if r['count'].shape[0] != n:
+            raise ValueError('draw: results for %d frames, %d frames' % (r['count'].shape[0], n))
+        prims, n_prims = pose_prims(r, crop_rect(h, w, crop), style)
+        draw_prims(d, prims, n_prims, torch.from_numpy(style.colours(bgr=bgr, nv12=x.matrix if nv12 else None)))
+        if on_device:
+            return frames
+        if nv12:
+            y, uv = d.y.cpu(), d.uv.cpu()
+            return NV12Frames(y, uv, x.matrix) if torch.is_tensor(x.y) else NV12Frames(y.numpy(), uv.numpy(), x.matrix)
+        out = d.cpu() if x.ndim == 4 else d[0].cpu()
+        return out if torch.is_tensor(x) else out.numpy()
+
+    def drawDetections(self, img, results):
+        """The reference's call (:175): one host BGR frame (H, W, 3) and its Results, drawn into ``img``,
+        which is returned.  The reference's text is not drawn."""
+        img[...] = self.draw(img, [results])
+        return img
 
     def detectFaces(self, frame):
         if is_uint8(frame):

@@ -8,8 +8,8 @@ uploaded as bytes; everything after the upload stays on the device.  Decoded vid
 luma plane and a half-resolution plane of interleaved U, V): ``NV12Frames`` wraps such frames, and
 everything that takes uint8 BGR frames takes one and does what it would do for the frames converted to
 BGR by the fixed-point rule of include/hpe.h, the conversion happening inside the gather (C ABI
-``hpe_preprocess_nv12`` / ``hpe_preprocess_rois_nv12``).  Image decoding, webcam capture and drawing
-stay out of scope.
+``hpe_preprocess_nv12`` / ``hpe_preprocess_rois_nv12``).  Drawing into such frames is hpe.draw's.  Image
+decoding and webcam capture stay out of scope.
 """
 import numpy as np
 import torch

@@ -417,6 +417,92 @@ int hpe_track(int64_t n_streams, int32_t n_frames, int32_t max_faces, const int3
               int32_t max_missed, int32_t max_tracks, int32_t *state_i, double *state_d, int32_t *track_out,
               double *boxes_out, double *keypoints_out, float *poses_out, void *stream);
 
+/* Detections and pose axes drawn into video frames on the device (csrc/hpe_draw.hip): the last stage of
+ * the reference's webcam loop, drawDetections (blazeFaceDetectorH5.py:175-219 with drawAxis_simo :64-77
+ * and EulerToMatrix :40-62).  Two stages: hpe_pose_prims turns detections into a table of integer
+ * primitives (float64 rules), hpe_draw / hpe_draw_nv12 rasterise any such table (pure integer).
+ *
+ * The primitive table: device memory (n_frames, P, HPE_DRAW_PRIM_WORDS) int32, row = (kind, x0, y0, x1,
+ * y1, size, colour, 0) in frame pixels; n_prims (n_frames) int32, of which min(max(n_prims[f], 0), P)
+ * leading rows of frame f are live.  Coverage of the pixel at integer (x, y), all in integers:
+ *   kind 1  rectangle outline: xa = min(x0, x1), xb = max(x0, x1), likewise ya, yb; th = size, h0 = th / 2,
+ *           h1 = (th - 1) / 2; covered iff inside [xa - h0, xb + h0] x [ya - h0, yb + h0] and not inside
+ *           the hole [xa + h1 + 1, xb - h1 - 1] x [ya + h1 + 1, yb - h1 - 1] (empty when its bounds cross)
+ *   kind 2  filled disk of radius r = size >= 0 about (x0, y0): (x - x0)^2 + (y - y0)^2 <= r^2
+ *   kind 3  thick segment P0 = (x0, y0) .. P1 = (x1, y1), th = size: d = P1 - P0, L2 = d.d, v = p - P0,
+ *           t = v.d;  t <= 0: 4 |v|^2 <= th^2;  t >= L2: 4 |p - P1|^2 <= th^2;  else 4 (vx dy - vy dx)^2
+ *           <= th^2 L2 in int64: the pixel centres within th / 2 of the segment; zero length is a dot
+ * A row is valid iff its kind is 1, 2 or 3, every coordinate has |c| <= HPE_DRAW_MAX_DIM, 1 <= size <=
+ * HPE_DRAW_MAX_SIZE (0 <= size for kind 2) and 0 <= colour < n_colours; any other row draws nothing, so
+ * a row of zeros is the legal filler.  With these bounds the largest term, 4 cross^2, is below 2^61.
+ * Nothing read from the table is used as an index before it is checked.  A pixel takes the colour of
+ * the highest-indexed valid live row that covers it (later rows paint over earlier ones); a pixel no
+ * row covers is not written at all.
+ * colours: device (n_colours, 4) uint8, byte 3 ignored.
+ * hpe_draw: frames of h x w pixels of 3 bytes, rows row_stride and frames frame_stride bytes apart;
+ * bytes 0..2 of the colour go to the pixel's three bytes (BGR or RGB is the caller's affair).
+ * hpe_draw_nv12: the plane layout of hpe_preprocess_nv12.  Byte 0 goes to the luma of every covered
+ * pixel; for each chroma pair uv[y >> 1][x >> 1], bytes 1 and 2 of the highest-indexed winning row over
+ * the block's four pixels are written as (U, V) if any of the four is covered, so thin lines keep
+ * their colour.  No colour conversion: the caller supplies (Y, U, V) bytes.
+ * No byte outside [row start, row start + 3 w) of a frame row (+ w for the NV12 planes) is written.
+ * Checked on the host (HPE_EINVAL, before any device call): negative n_frames or P, h or w outside 1 ..
+ * HPE_DRAW_MAX_DIM (or odd, NV12), row strides below the row's bytes, negative frame strides, n_colours
+ * outside 1..256, n_frames beyond int32, n_frames * P * HPE_DRAW_PRIM_WORDS or a frame's last byte offset
+ * beyond int64, null pointers when there is work.  n_frames == 0 or P == 0 is a no-op.
+ *
+ * hpe_pose_prims: count (n_images), boxes (n_images, max_faces, 4) f64 [x1,y1,x2,y2], keypoints
+ * (n_images, max_faces, 6, 2) f64, poses (n_images, max_faces, 3) f32 (yaw, pitch, roll), as hpe_detect,
+ * hpe_merge_rois or hpe_track wrote them, normalised to the source rectangle (src_x0, src_y0, src_w,
+ * src_h) in frame pixels as for hpe_face_rois -> prims (n_images, P = max_faces * HPE_DRAW_FACE_PRIMS,
+ * 8) and n_prims[i] = 11 c, c = min(max(count[i], 0), max_faces).  Detection j owns rows 11 j .. 11 j +
+ * 10: box, keypoints 0..5, axis X, axis Y, axis Z, with the colour indices 0, 1, 2 / 3 / 4, then one
+ * reserved row that is written as zeros (ten primitives in a stride of 11).  A kind-0 row is always
+ * written as eight zeros.  Rows at or past 11 c are not written.  In float64, every operation rounded on its own, floats converted exactly:
+ *   pix(v, s, o) = o + (int) clamp(trunc(s * v), -2^30, 2^30), then clamped to +-HPE_DRAW_MAX_DIM
+ *   box      x1 = pix(bx1, src_w, src_x0), y1 = pix(by1, src_h, src_y0), likewise x2, y2 (the reference's
+ *            (img_width * box[0]).astype(int), truncation toward zero): row (1, x1, y1, x2, y2, box_th, 0, 0)
+ *   keypoint (kx, ky) = (pix(., src_w, src_x0), pix(., src_h, src_y0)): row (2, kx, ky, kx, ky, kp_radius, 1, 0)
+ *   axes     tdx = (x1 + x2) / 2.0, tdy = (y1 + y2) / 2.0, cx = trunc(tdx), cy = trunc(tdy),
+ *            size = trunc(min(x2 - x1, y2 - y1) / 2.0) (negative for flipped corners, used as it is);
+ *            r = (-roll) / 180 * pi, y = (-yaw) / 180 * pi, p = (-pitch) / 180 * pi (pi the nearest double);
+ *            m00 = cy cr, m10 = (sp sy) cr + cp sr, m01 = -(cy sr), m11 = -((sp sy) sr) + cp cr, m02 = sy,
+ *            m12 = -(sp cy);  X ends at (trunc(m00 size + tdx), trunc(-(m10 size) + tdy)), Y at
+ *            (trunc(-(m01 size) + tdx), trunc(m11 size + tdy)), Z at (trunc(m02 size + tdx),
+ *            trunc(-(m12 size) + tdy)), each clamped to +-HPE_DRAW_MAX_DIM: rows (3, cx, cy, ex, ey,
+ *            axis_th_*, 2 | 3 | 4, 0)
+ * A box_th of 0, a negative kp_radius or an axis_th_* of 0 writes kind 0 for those rows.  A non-finite
+ * box coordinate makes all 11 rows kind 0, a non-finite keypoint coordinate its own row, a non-finite
+ * angle the three axis rows.
+ * Two facts about this rule.  (1) The closed form is Rx Ry Rz of EulerToMatrix(-roll, -yaw, -pitch) with
+ * the exact zero and one terms dropped; its entries differ from np.matmul's by a rounding for about half
+ * of random poses (CPU, 20,000 random poses and boxes on a 1920 x 1080 frame: 9,574 poses differ in some
+ * entry, zero truncated endpoints differ).  (2) The device's float64 sin / cos may differ from the
+ * host's by an ulp, so an endpoint whose untruncated value lies within that distance of an integer can
+ * land one pixel away: parity with the reference holds for the integer table except for such values.
+ * Parity with OpenCV's own line, circle and rectangle rasterisation is unpinned: the coverage rules
+ * above are this project's.
+ * Out of scope: the text the reference puts on the frame (score, Yaw / Pitch / Roll, FPS; it needs
+ * OpenCV's Hershey font data), anti-aliasing, alpha blending, and the unused draw_axis method (:142-172).
+ * Checked on the host (HPE_EINVAL): negative n_images, max_faces < 1, src_w or src_h outside 1 .. 2^24,
+ * |src_x0| or |src_y0| above 2^24, thicknesses outside 0 .. HPE_DRAW_MAX_SIZE, kp_radius outside -1 ..
+ * HPE_DRAW_MAX_SIZE, n_images * max_faces * 11 beyond int32, null pointers when n_images > 0.
+ * n_images == 0 is a no-op. */
+#define HPE_DRAW_PRIM_WORDS 8
+#define HPE_DRAW_FACE_PRIMS 11
+#define HPE_DRAW_MAX_DIM 8192
+#define HPE_DRAW_MAX_SIZE 64
+int hpe_draw(uint8_t *frames, int64_t n_frames, int32_t h, int32_t w, int64_t row_stride, int64_t frame_stride,
+             const int32_t *prims, const int32_t *n_prims, int32_t P, const uint8_t *colours, int32_t n_colours,
+             void *stream);
+int hpe_draw_nv12(uint8_t *y, uint8_t *uv, int64_t n_frames, int32_t h, int32_t w, int64_t y_row_stride,
+                  int64_t y_frame_stride, int64_t uv_row_stride, int64_t uv_frame_stride, const int32_t *prims,
+                  const int32_t *n_prims, int32_t P, const uint8_t *colours, int32_t n_colours, void *stream);
+int hpe_pose_prims(const int32_t *count, const double *boxes, const double *keypoints, const float *poses,
+                   int64_t n_images, int32_t max_faces, int32_t src_x0, int32_t src_y0, int32_t src_w,
+                   int32_t src_h, int32_t box_th, int32_t kp_radius, int32_t axis_th_x, int32_t axis_th_y,
+                   int32_t axis_th_z, int32_t *prims, int32_t *n_prims, void *stream);
+
 const char *hpe_last_error(void);
 
 /* Build stamp: "src=<sha256/16 of the library's sources> git=<commit>[-dirty]" (csrc/Makefile).  The
