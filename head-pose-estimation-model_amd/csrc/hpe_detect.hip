@@ -7,14 +7,12 @@
 //                      IoU in fp32 on the fp32-cast boxes, corner order agnostic, zero area ->
 //                      IoU 0, suppress iff IoU > threshold                                 :332
 //   pose gather        detection index -> pose cell of the 16x16 / 8x8 regressor map       :342-353
-// Every operation rounds on its own (contraction is off in this file, as in hpe_merge.hip): the IoU
-// is inter / ((area_i + area_j) - inter) with inter = h * w rounded to fp32 before it is subtracted,
-// as TensorFlow's kernel and oracle.detector_ref._iou have it.  A fused multiply-add in the
-// denominator moves the IoU by one ulp for about 8 % of overlapping pairs and flips the decision for
-// a pair whose IoU is the threshold.  The fp64 decode does not depend on the setting: its multiplies
-// (by 128, 0.5) are exact.
-// Candidates are compacted and bitonic-sorted in LDS (64-bit keys: ordered score, ~index); the
-// greedy pass suppresses in parallel across the workgroup, one barrier pair per kept box.
+// The IoU, the sort key, the bitonic sort and the greedy pass are hpe_boxes.h's, shared with
+// hpe_merge_rois and hpe_track.  Nothing in this file depends on the contraction setting: the IoU
+// carries its own, and the fp64 decode's multiplies (by 128, 0.5) are exact.
+// Candidates are compacted and bitonic-sorted in LDS over the power of two that holds them (64-bit
+// keys: ordered score, ~index); the greedy pass finds the next kept box by ballot and suppresses in
+// parallel across the workgroup, one barrier per kept box.
 // Non-finite loc values are not rejected and lie outside the parity claim: fminf / fmaxf return the
 // other operand for a NaN (Eigen's mini / maxi in TensorFlow's kernel depend on the operand order),
 // a NaN area fails area > 0 and gives IoU 0, and a NaN IoU never suppresses.  Such a frame's count
@@ -24,9 +22,8 @@
 #include <stdint.h>
 
 #include "../../include/hpe.h"
+#include "hpe_boxes.h"
 #include "hpe_common.h"
-
-#pragma clang fp contract(off)
 
 #define DET_N0 512     // 16 x 16 cells x 2 anchors (stride 8)
 #define DET_N1 384      // 8 x 8 cells x 6 anchors (strides 16, 16, 16 merged)
@@ -48,11 +45,6 @@ struct DetArgs {
   float* poses;
 };
 
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ void anchor_center(int d, double* ax, double* ay) {
   if (d < DET_N0) {
     const int cell = d >> 1;
@@ -69,17 +61,10 @@ __global__ void __launch_bounds__(DET_T) detect_kernel(DetArgs a) {
   __shared__ uint64_t key[DET_SORT];
   __shared__ float fb[DET_N][4];        // fp32 boxes (NMS input), by detection index
   __shared__ int sup[DET_SORT];
-  __shared__ int ncand, nsel, cur_keep;
+  __shared__ int ncand;
   const int64_t img = blockIdx.x;
   const int t = threadIdx.x;
-  if (t == 0) {
-    ncand = 0;
-    nsel = 0;
-  }
-  for (int i = t; i < DET_SORT; i += DET_T) {
-    key[i] = 0;
-    sup[i] = 0;
-  }
+  if (t == 0) ncand = 0;
   __syncthreads();
   // ---- threshold + compaction ----
   for (int d = t; d < DET_N; d += DET_T) {
@@ -87,7 +72,7 @@ __global__ void __launch_bounds__(DET_T) detect_kernel(DetArgs a) {
     if (logit > a.thr) {
       const float sc = 1.0f / (1.0f + expf(-logit));
       const int slot = atomicAdd(&ncand, 1);
-      key[slot] = ((uint64_t)f2ord(sc) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)d);
+      key[slot] = box_key(sc, d);
       const float* lp = d < DET_N0 ? a.loc0 + (img * DET_N0 + d) * DET_LOC : a.loc1 + (img * DET_N1 + d - DET_N0) * DET_LOC;
       double ax, ay;
       anchor_center(d, &ax, &ay);
@@ -102,59 +87,19 @@ __global__ void __launch_bounds__(DET_T) detect_kernel(DetArgs a) {
   }
   __syncthreads();
   const int n = ncand;
-  // ---- bitonic sort, descending (score desc, then index asc) ----
-  for (int k = 2; k <= DET_SORT; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = t; i < DET_SORT; i += DET_T) {
-        const int p = i ^ j;
-        if (p > i) {
-          const uint64_t x = key[i], y = key[p];
-          const bool desc = (i & k) == 0;
-          if (desc ? (x < y) : (x > y)) {
-            key[i] = y;
-            key[p] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // ---- greedy NMS ----
-  for (int i = 0; i < n; ++i) {
-    if (nsel >= a.max_faces) break;   // uniform: read after the barrier below
-    if (sup[i]) continue;             // uniform
-    const int di = (int)(0xFFFFFFFFu - (uint32_t)key[i]);
-    if (t == 0) {
-      cur_keep = nsel;
-      const int64_t o = img * a.max_faces + nsel;
-      a.det_index[o] = di;
-      a.scores[o] = __uint_as_float((uint32_t)(key[i] >> 32) & 0x80000000u ? (uint32_t)(key[i] >> 32) & 0x7FFFFFFFu
-                                                                             : ~(uint32_t)(key[i] >> 32));
-    }
-    const float ymin_i = fminf(fb[di][0], fb[di][2]), xmin_i = fminf(fb[di][1], fb[di][3]);
-    const float ymax_i = fmaxf(fb[di][0], fb[di][2]), xmax_i = fmaxf(fb[di][1], fb[di][3]);
-    const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
-    for (int j = i + 1 + t; j < n; j += DET_T) {
-      if (sup[j]) continue;
-      const int dj = (int)(0xFFFFFFFFu - (uint32_t)key[j]);
-      const float ymin_j = fminf(fb[dj][0], fb[dj][2]), xmin_j = fminf(fb[dj][1], fb[dj][3]);
-      const float ymax_j = fmaxf(fb[dj][0], fb[dj][2]), xmax_j = fmaxf(fb[dj][1], fb[dj][3]);
-      const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
-      float iou = 0.f;
-      if (area_i > 0.f && area_j > 0.f) {
-        const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
-        const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
-        const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
-        iou = inter / (area_i + area_j - inter);
-      }
-      if (iou > a.iou) sup[j] = 1;
-    }
-    __syncthreads();
-    if (t == 0) nsel = nsel + 1;
-    __syncthreads();
-  }
+  int p2 = 1;
+  while (p2 < n) p2 <<= 1;
+  for (int i = n + t; i < p2; i += DET_T) key[i] = 0;   // below every candidate's key
+  for (int i = t; i < n; i += DET_T) sup[i] = 0;
   __syncthreads();
-  const int ns = nsel;
+  // ---- sort (score desc, then index asc) and greedy NMS; n == 0 keeps nothing ----
+  bitonic_sort_desc(key, p2, t, DET_T);
+  const int64_t o0 = img * a.max_faces;
+  const int ns = greedy_nms(key, fb, sup, n, a.iou, a.max_faces, t, DET_T, [&](int s, uint64_t k) {
+    a.det_index[o0 + s] = key_index(k);
+    a.scores[o0 + s] = key_score(k);
+  });
+  __syncthreads();   // det_index (thread 0's stores) is read by the workgroup below
   if (t == 0) a.count[img] = ns;
   // ---- fp64 boxes / keypoints and pose gather for the kept detections ----
   for (int s = t; s < ns; s += DET_T) {

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/hpe.h"
+#include "hpe_boxes.h"
 #include "hpe_common.h"
 
 #pragma clang fp contract(off)
@@ -377,11 +378,9 @@ extern "C" int hpe_pose_prims(const int32_t* count, const double* boxes, const d
                               int64_t n_images, int32_t max_faces, int32_t src_x0, int32_t src_y0, int32_t src_w,
                               int32_t src_h, int32_t box_th, int32_t kp_radius, int32_t axis_th_x, int32_t axis_th_y,
                               int32_t axis_th_z, int32_t* prims, int32_t* n_prims, void* stream) {
-  const int32_t lim = 1 << 24;
   if (n_images < 0) return hpe_fail(HPE_EINVAL, "hpe_pose_prims: negative image count");
   if (max_faces < 1) return hpe_fail(HPE_EINVAL, "hpe_pose_prims: max_faces %d must be positive", max_faces);
-  if (src_w < 1 || src_w > lim || src_h < 1 || src_h > lim || src_x0 < -lim || src_x0 > lim || src_y0 < -lim ||
-      src_y0 > lim)
+  if (!roi_rect_ok(src_x0, src_y0, src_w, src_h))
     return hpe_fail(HPE_EINVAL, "hpe_pose_prims: source rectangle (%d, %d, %d, %d) outside 1 .. 2^24 / +-2^24", src_x0,
                     src_y0, src_w, src_h);
   if (box_th < 0 || box_th > HPE_DRAW_MAX_SIZE || axis_th_x < 0 || axis_th_x > HPE_DRAW_MAX_SIZE || axis_th_y < 0 ||

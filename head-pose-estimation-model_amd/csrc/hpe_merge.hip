@@ -3,17 +3,16 @@
 // back into the frame's coordinates and merged by one NMS, one workgroup per frame.
 //   candidates  (r, j), r < R table rows of the frame, j < min(max(count[f*R + r], 0), M); a row must
 //               pass hpe_preprocess_rois' validity rule and name frame f, else it contributes nothing
-//   remap       float64, every operation rounded on its own (contraction is off in this file):
+//   remap       float64, every operation rounded on its own (contraction is off in this file for
+//               this: a fused o + v * s would round once):
 //               X = ((rx + x * rw) - dst_x0) / dst_w, Y = ((ry + y * rh) - dst_y0) / dst_h
 //               for the two box corners and the six keypoints
 //   dropped     a candidate with a non-finite remapped box coordinate or a NaN score
 //   order       score descending, then r * M + j ascending (64-bit keys: ordered score, ~index)
-//   NMS         hpe_detect's: greedy, IoU in fp32 on the fp32 casts of the remapped boxes, corner
-//               order agnostic, zero area -> IoU 0, suppress iff IoU > threshold, at most
-//               max_faces_out kept
-// Compaction, a bitonic sort in LDS over the power of two that holds the frame's candidates, then the
-// greedy pass: every wave finds the next unsuppressed candidate by a ballot over 64 flags, the
-// workgroup suppresses in parallel, one barrier per kept box.  A latency kernel: the cost of tiled
+//   NMS         hpe_detect's (hpe_boxes.h: the same key, sort, greedy pass and IoU), on the fp32 casts
+//               of the remapped boxes, at most max_faces_out kept
+// Compaction, the bitonic sort in LDS over the power of two that holds the frame's candidates, then the
+// greedy pass.  A latency kernel: the cost of tiled
 // detection is the backbone over R images per frame, not this.
 // LDS (dynamic): keys 8 B x pow2(R * M), fp32 boxes 16 B and a flag 4 B x R * M: 112 KB at
 // HPE_MERGE_MAX_CAND.
@@ -21,13 +20,13 @@
 #include <stdint.h>
 
 #include "../../include/hpe.h"
+#include "hpe_boxes.h"
 #include "hpe_common.h"
 
 #pragma clang fp contract(off)
 
 #define MRG_T 256
 #define MRG_KP 6
-#define MRG_LIM (1 << 24)   // the ROI validity bound of hpe_preprocess_rois
 
 struct MergeArgs {
   const int32_t* rois;
@@ -47,17 +46,6 @@ struct MergeArgs {
   double* keypoints_out;
   float* poses_out;
 };
-
-__device__ __forceinline__ uint32_t mrg_f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// row (frame, x0, y0, w, h) of frame f's table: valid as hpe_preprocess_rois has it, and of this frame
-__device__ __forceinline__ bool mrg_row_ok(const int32_t* roi, int64_t f) {
-  return roi[0] == f && roi[3] >= 1 && roi[3] <= MRG_LIM && roi[4] >= 1 && roi[4] <= MRG_LIM &&
-         roi[1] >= -MRG_LIM && roi[1] <= MRG_LIM && roi[2] >= -MRG_LIM && roi[2] <= MRG_LIM;
-}
 
 // one coordinate from ROI-normalised to destination-normalised: ((o + v * s) - d0) / d
 __device__ __forceinline__ double mrg_map(double v, double o, double s, double d0, double d) {
@@ -80,7 +68,7 @@ __global__ void __launch_bounds__(MRG_T) merge_rois_kernel(MergeArgs a) {
     const int r = c / a.M, j = c - r * a.M;
     if (j >= a.count[row0 + r]) continue;   // also a negative count; j < M bounds a count above M
     const int32_t* roi = a.rois + (row0 + r) * 5;
-    if (!mrg_row_ok(roi, f)) continue;
+    if (roi[0] != f || !roi_rect_ok(roi[1], roi[2], roi[3], roi[4])) continue;   // not a valid row of this frame
     const int64_t s = (row0 + r) * a.M + j;
     const float sc = a.scores[s];
     const double* bo = a.boxes + s * 4;
@@ -89,8 +77,7 @@ __global__ void __launch_bounds__(MRG_T) merge_rois_kernel(MergeArgs a) {
     const double x2 = mrg_map(bo[2], rx, rw, a.dx0, a.dw), y2 = mrg_map(bo[3], ry, rh, a.dy0, a.dh);
     if (!(isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2)) || sc != sc) continue;
     const int slot = atomicAdd(&ncand, 1);
-    // sc + 0.0f: -0.0f orders as +0.0f, as a comparison of the scores has it
-    key[slot] = ((uint64_t)mrg_f2ord(sc + 0.0f) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)c);
+    key[slot] = box_key(sc, c);
     fb[c][0] = (float)x1;
     fb[c][1] = (float)y1;
     fb[c][2] = (float)x2;
@@ -107,66 +94,14 @@ __global__ void __launch_bounds__(MRG_T) merge_rois_kernel(MergeArgs a) {
   for (int i = n + t; i < p2; i += MRG_T) key[i] = 0;   // below every candidate's key
   for (int i = t; i < n; i += MRG_T) sup[i] = 0;
   __syncthreads();
-  // ---- bitonic sort of key[0 .. p2), descending (score desc, then index asc), one pair per step ----
-  for (int k = 2; k <= p2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int q = t; q < (p2 >> 1); q += MRG_T) {
-        const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-        const int p = i | j;
-        const uint64_t x = key[i], y = key[p];
-        const bool desc = (i & k) == 0;
-        if (desc ? (x < y) : (x > y)) {
-          key[i] = y;
-          key[p] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // ---- greedy NMS: i and ns are uniform (every thread reads the same flags between barriers) ----
-  const int lane = t & 63;
-  int ns = 0;
-  int i = 0;
-  while (i < n && ns < a.max_out) {
-    // the first unsuppressed position >= i, 64 flags at a time.  Flags of positions above the one
-    // found may already be changing (a wave ahead of this one suppressing against it); those below
-    // it, and its own, are stable
-    const int base = i & ~63;
-    const int pos = base + lane;
-    const unsigned long long m = __ballot(pos >= i && pos < n && !sup[pos]);
-    if (!m) {
-      i = base + 64;
-      continue;
-    }
-    i = base + __ffsll(m) - 1;
-    const int ci = (int)(0xFFFFFFFFu - (uint32_t)key[i]);
-    if (t == 0) a.src_out[f * a.max_out + ns] = ci;
-    const float ymin_i = fminf(fb[ci][0], fb[ci][2]), xmin_i = fminf(fb[ci][1], fb[ci][3]);
-    const float ymax_i = fmaxf(fb[ci][0], fb[ci][2]), xmax_i = fmaxf(fb[ci][1], fb[ci][3]);
-    const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
-    for (int j = i + 1 + t; j < n; j += MRG_T) {
-      if (sup[j]) continue;
-      const int cj = (int)(0xFFFFFFFFu - (uint32_t)key[j]);
-      const float ymin_j = fminf(fb[cj][0], fb[cj][2]), xmin_j = fminf(fb[cj][1], fb[cj][3]);
-      const float ymax_j = fmaxf(fb[cj][0], fb[cj][2]), xmax_j = fmaxf(fb[cj][1], fb[cj][3]);
-      const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
-      float iou = 0.f;
-      if (area_i > 0.f && area_j > 0.f) {
-        const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
-        const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
-        const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
-        iou = inter / (area_i + area_j - inter);
-      }
-      if (iou > a.iou) sup[j] = 1;
-    }
-    ++ns;
-    ++i;
-    __syncthreads();
-  }
+  // ---- sort (score desc, then index asc) and greedy NMS ----
+  bitonic_sort_desc(key, p2, t, MRG_T);
+  const int64_t o0 = f * a.max_out;
+  const int ns = greedy_nms(key, fb, sup, n, a.iou, a.max_out, t, MRG_T,
+                            [&](int s, uint64_t k) { a.src_out[o0 + s] = key_index(k); });
   __syncthreads();   // src_out (thread 0's stores) is read by the workgroup below
   if (t == 0) a.count_out[f] = ns;
   // ---- the kept detections: score and pose copied, box corners and keypoints remapped in fp64 ----
-  const int64_t o0 = f * a.max_out;
   for (int s = t; s < ns; s += MRG_T) {
     const int c = a.src_out[o0 + s];
     const int64_t in = row0 * a.M + c;   // (row0 + r) * M + j
@@ -202,8 +137,7 @@ extern "C" int hpe_merge_rois(const int32_t* rois, int64_t n_frames, int32_t row
                     rows_per_frame, max_faces_in, max_faces_out);
   if (dst_w <= 0 || dst_h <= 0)
     return hpe_fail(HPE_EINVAL, "hpe_merge_rois: destination rectangle %d x %d must be positive", dst_w, dst_h);
-  if (dst_w > MRG_LIM || dst_h > MRG_LIM || dst_x0 > MRG_LIM || dst_x0 < -MRG_LIM || dst_y0 > MRG_LIM ||
-      dst_y0 < -MRG_LIM)
+  if (!roi_rect_ok(dst_x0, dst_y0, dst_w, dst_h))
     return hpe_fail(HPE_EINVAL, "hpe_merge_rois: destination rectangle (%d, %d, %d, %d) beyond 2^24", dst_x0, dst_y0,
                     dst_w, dst_h);
   if ((int64_t)rows_per_frame * max_faces_in > HPE_MERGE_MAX_CAND)

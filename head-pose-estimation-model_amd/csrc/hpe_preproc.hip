@@ -8,8 +8,9 @@
 //   weights of taps loc-1 .. loc+2: Keys cubic (A = -0.5) at off / 1024 and (1024 - off) / 1024 (the
 //   values of TF's 1025 x 2 coefficient table, evaluated in place), taps clamped to the crop, a
 //   clamped tap's weight 0, the rest divided by their sum; y pass over the four tap columns, then x.
-// Every fp32 operation is rounded on its own: the file is compiled with contraction off, so no
-// multiply-add pair becomes an FMA (the only fused ops left are inside the division expansions).
+// Every fp32 operation is rounded on its own: the file is compiled with contraction off (the weights,
+// the filter passes, the NV12 conversion and hpe_face_rois' float64 need it), so no multiply-add pair
+// becomes an FMA (the only fused ops left are inside the division expansions).
 // One thread per output pixel (three channels), lanes along x; a gather bounded by load latency.
 // Two kernels around one body: preprocess_kernel (one crop for the batch) and preprocess_rois_kernel
 // (one row of a device table of regions of interest per output, which may reach outside the frame)
@@ -23,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/hpe.h"
+#include "hpe_boxes.h"
 #include "hpe_common.h"
 
 #pragma clang fp contract(off)
@@ -179,7 +181,7 @@ __global__ void __launch_bounds__(PRE_T) preprocess_kernel(PreArgs a) {
 // r = (frame, x0, y0, w, h) of a device table.  The kernel is the shared body around its own gather
 // (taps clamp to the canvas, not to the frame), so an ROI inside the frame equals hpe_preprocess with
 // that crop and an ROI reaching outside equals hpe_preprocess on a host-padded copy, bit for bit.
-#define ROI_LIM (1 << 24)   // |x0|, |y0|, w, h <= 2^24: every coordinate sum below fits int32
+// A row's rectangle must pass roi_rect_ok (hpe_boxes.h): every coordinate sum below then fits int32.
 
 struct RoiArgs {           // filled by hpe_preprocess_rois in this order, one line there per line here
   const uint8_t* frames;
@@ -202,8 +204,7 @@ __global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
   const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
   float* dst = a.out + (int64_t)p.pix * 3;
   const uint8_t pad[3] = {(uint8_t)a.pad0, (uint8_t)a.pad1, (uint8_t)a.pad2};
-  const bool valid = fr >= 0 && fr < a.n_frames && cw >= 1 && cw <= ROI_LIM && ch >= 1 && ch <= ROI_LIM &&
-                     x0 >= -ROI_LIM && x0 <= ROI_LIM && y0 >= -ROI_LIM && y0 <= ROI_LIM;
+  const bool valid = fr >= 0 && fr < a.n_frames && roi_rect_ok(x0, y0, cw, ch);
   if (!valid) {   // reads no frame memory
     float o[3];
 #pragma unroll
@@ -429,8 +430,7 @@ __global__ void __launch_bounds__(PRE_T) preprocess_rois_nv12_kernel(RoiNv12Args
   const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
   float* dst = a.out + (int64_t)p.pix * 3;
   const uint8_t pad[3] = {(uint8_t)a.pad_b, (uint8_t)a.pad_g, (uint8_t)a.pad_r};
-  const bool valid = fr >= 0 && fr < a.n_frames && cw >= 1 && cw <= ROI_LIM && ch >= 1 && ch <= ROI_LIM &&
-                     x0 >= -ROI_LIM && x0 <= ROI_LIM && y0 >= -ROI_LIM && y0 <= ROI_LIM;
+  const bool valid = fr >= 0 && fr < a.n_frames && roi_rect_ok(x0, y0, cw, ch);
   if (!valid) {   // reads no frame memory
     float o[3];
 #pragma unroll
@@ -678,7 +678,7 @@ __global__ void __launch_bounds__(FROI_T) face_rois_kernel(const int32_t* count,
       const double side = scale * fmax(px2 - px1, py2 - py1);
       int32_t* o = rois + (first + j) * 5;
       if (isfinite(cx) && isfinite(cy) && isfinite(side)) {
-        const double lim = (double)ROI_LIM;
+        const double lim = (double)HPE_ROI_LIM;
         const double S = fmin(fmax(ceil(side), 1.0), lim);
         const double rx = fmin(fmax(floor(cx - 0.5 * S), -lim), lim);
         const double ry = fmin(fmax(floor(cy - 0.5 * S), -lim), lim);

@@ -8,11 +8,11 @@
 //   state       per stream K track slots: id (< 0: free), miss count, 19 smoothed doubles (box 4,
 //               keypoints 12, pose 3) and the last matched raw box (4 doubles); next_id per stream
 //   invalid     a detection with a non-finite box coordinate: id -1, outputs bit copies of the inputs
-//   match       live tracks not yet matched in this frame; u = hpe_detect's IoU (fp32 on the fp32 casts
-//               of the detection's box and the track's last raw box, corner order agnostic, zero area
-//               -> 0); qualifies iff u > match_iou; largest u, then lowest slot
+//   match       live tracks not yet matched in this frame; u = hpe_detect's IoU (hpe_boxes.h's box_iou)
+//               of the fp32 casts of the detection's box and the track's last raw box; qualifies iff
+//               u > match_iou; largest u, then lowest slot
 //   update      state = alpha * m + (1.0 - alpha) * state in float64, each operation rounded on its own
-//               (contraction is off in this file), 1.0 - alpha computed once: EMAFilter.update
+//               (contraction is off in this file for this), 1.0 - alpha computed once: EMAFilter.update
 //   spawn       nothing matched: lowest free slot, id = next_id, next_id = (next_id + 1) & 0x7fffffff,
 //               state = m; no free slot: id -1, outputs bit copies of the inputs
 //   frame end   every live unmatched track: miss += 1, freed (id = -1) iff miss > max_missed; a freed
@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "../../include/hpe.h"
+#include "hpe_boxes.h"
 #include "hpe_common.h"
 
 #pragma clang fp contract(off)
@@ -126,19 +127,8 @@ __global__ void __launch_bounds__(TRK_T) track_kernel(TrackArgs a) {
       bool hit = false;   // matched an existing track (uniform)
       if (isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3)) {
         const float f0 = (float)b0, f1 = (float)b1, f2 = (float)b2, f3 = (float)b3;
-        const float ymin_i = fminf(f0, f2), xmin_i = fminf(f1, f3);
-        const float ymax_i = fmaxf(f0, f2), xmax_i = fmaxf(f1, f3);
-        const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
-        const float ymin_j = fminf(r0, r2), xmin_j = fminf(r1, r3);
-        const float ymax_j = fmaxf(r0, r2), xmax_j = fmaxf(r1, r3);
-        const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
-        float u = 0.f;
-        if (area_i > 0.f && area_j > 0.f) {
-          const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
-          const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
-          const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
-          u = inter / (area_i + area_j - inter);
-        }
+        const float fd[4] = {f0, f1, f2, f3}, fr[4] = {r0, r1, r2, r3};
+        const float u = box_iou(fd, fr);
         const bool q = id >= 0 && !matched && u > a.iou;
         const uint32_t ub = __float_as_uint(u);
         unsigned long long cand = __ballot(q);

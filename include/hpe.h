@@ -217,6 +217,8 @@ int hpe_blazeface_forward(const hpe_blazeface *h, const float *params, const flo
  *   decode boxes / 6 keypoints against the 896 SSD anchors in fp64, greedy NMS with
  *   tf.image.non_max_suppression semantics (IoU in fp32, suppress iff IoU > iou_threshold, at most
  *   max_faces kept), and gather each kept detection's pose from its 16x16 / 8x8 regressor cell.
+ *   The IoU, the score order and the greedy pass are defined once, in csrc/hpe_boxes.h, for this
+ *   function, hpe_merge_rois and hpe_track.
  * Inputs (device): cls0 (n,512), cls1 (n,384), loc0 (n,512,16), loc1 (n,384,16), pose0 (n,16,16,3),
  * pose1 (n,8,8,3).  Outputs (device, per frame max_faces slots, the first count[i] valid, in NMS
  * selection order): det_index int32, scores f32, boxes f64 [x1,y1,x2,y2], keypoints f64 [6][2],
@@ -347,8 +349,9 @@ int hpe_face_rois(const int32_t *count, const double *boxes, int64_t n_images, i
  *   X = ((rx + x * rw) - dst_x0) / dst_w,  Y = ((ry + y * rh) - dst_y0) / dst_h
  * for the two box corners and the six keypoints.  A candidate is dropped if a remapped box coordinate
  * is not finite or its score is NaN.  Order: score descending, then r*M + j ascending.  NMS: that of
- * the detector post-processing (greedy, IoU in fp32 on the fp32 casts of the remapped boxes, corner
- * order agnostic, zero area gives IoU 0, suppress iff IoU > iou_threshold), at most max_faces_out kept.
+ * the detector post-processing, the same code (csrc/hpe_boxes.h: greedy, IoU in fp32 on the fp32 casts
+ * of the remapped boxes, corner order agnostic, zero area gives IoU 0, suppress iff IoU >
+ * iou_threshold), at most max_faces_out kept.
  * Outputs (device, per frame max_faces_out slots, the first count_out[f] valid, in selection order; the
  * slots past it are not written): src_out int32 = r*M + j, scores_out / poses_out bit copies, boxes_out
  * f64 [x1,y1,x2,y2] and keypoints_out f64 [6][2] remapped.
@@ -386,10 +389,10 @@ int hpe_merge_rois(const int32_t *rois, int64_t n_frames, int32_t rows_per_frame
  *   invalid  a box coordinate that is not finite: matches nothing, spawns nothing; track_out -1 and
  *            the outputs are bit copies of the inputs
  *   match    among the live tracks not yet matched in this frame, u = IoU of the detection's box and
- *            the track's last raw box, both cast to fp32, by the detector's formula (corner order
- *            agnostic, zero area gives 0, as hpe_merge_rois); a track qualifies iff u > match_iou; the
- *            largest u wins, on a tie the lowest slot.  A negative match_iou lets a zero overlap match:
- *            with one face that is the reference's position-only filter
+ *            the track's last raw box, both cast to fp32, by the detector's formula (box_iou of
+ *            csrc/hpe_boxes.h: corner order agnostic, zero area gives 0); a track qualifies iff
+ *            u > match_iou; the largest u wins, on a tie the lowest slot.  A negative match_iou lets a
+ *            zero overlap match: with one face that is the reference's position-only filter
  *   update   on a match, each of the 19 values: state = alpha * m + (1.0 - alpha) * state in float64,
  *            three separately rounded operations, 1.0 - alpha computed once (EMAFilter.update)
  *   spawn    when nothing matches, the lowest free slot if there is one: id = next_id, next_id =

@@ -84,6 +84,23 @@ def test_restatement_iou_equals_oracle_iou():
     for i in range(len(b)):
         assert got[i].tobytes() == D._iou(b[i, 0], b[i, 1]).tobytes()
     assert (got > 0).sum() > 100 and (got == 0).sum() > 40
+    # The areas that are not positive, on either side (tests/track_ref.py leans on this too): zero
+    # (no width, no height, a point) and NaN (inf - inf from float64 values beyond the float32 range,
+    # inf * 0 from a height that overflows on a box of no width).  The kernels' rule is IoU 0; the oracle
+    # gives 0 for the zero areas and lets a NaN area through as a NaN IoU, which suppresses and matches
+    # nothing either.
+    big = F4(3e38)
+    good = F4([0.1, 0.2, 0.5, 0.7])
+    odd = {'no width': F4([0.1, 0.3, 0.5, 0.3]), 'no height': F4([0.4, 0.2, 0.4, 0.7]),
+           'a point': F4([0.3, 0.3, 0.3, 0.3]), 'inf - inf': F4([np.inf, 0.2, np.inf, 0.7]),
+           'inf * 0': F4([-big, 0.3, big, 0.3]), '-inf - -inf': F4([0.1, -np.inf, 0.5, -np.inf])}
+    for name, o in odd.items():
+        for bi, bj in ((o, good), (good, o), (o, o), (o[[2, 3, 0, 1]], good)):
+            v = R.iou(bi, bj)
+            assert v.dtype == F4 and v.tobytes() == F4(0).tobytes(), name
+            with np.errstate(all='ignore'):
+                w = D._iou(bi, bj)
+            assert w.tobytes() == F4(0).tobytes() if 'inf' not in name else np.isnan(w), name
 
 
 def test_cases_expected_shape(cases):
@@ -368,14 +385,37 @@ def test_gpu_detect_nonfinite_loc_stays_in_its_frame(cases):
         assert (a1[~nan].tobytes() == a3[~nan].tobytes()), k
 
 
-@pytest.mark.gpu
-def test_gpu_merge_runs_the_same_nms(cases):
-    """hpe_merge_rois with a 1 x 1 ROI and a 1 x 1 destination remaps by ((0 + x * 1) - 0) / 1, the
-    identity in bits, so fed a frame's thresholded candidates (float64 boxes, the reference's scores,
-    index order) it must keep what hpe_detect keeps, in the same order."""
+def gpu_merge_identity(scores, boxes, kps, iou, K, rows, M):
+    """hpe_merge_rois on one frame of `rows` table rows, each the 1 x 1 ROI, with a 1 x 1 destination: the
+    remap is ((0 + x * 1) - 0) / 1, the identity in bits.  The candidates (float32 scores, float64 boxes
+    and keypoints) fill the rows' M slots in order.  Returns (src_out, boxes_out) of the kept ones."""
     import torch
     lib = _lib.load()
     p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    n = len(scores)
+    assert n <= rows * M
+    count = np.asarray([min(max(n - r * M, 0), M) for r in range(rows)], np.int32)
+    pad = lambda a: np.concatenate([a, np.zeros((rows * M - n,) + a.shape[1:], a.dtype)])   # noqa: E731
+    rois = np.tile(np.asarray([0, 0, 0, 1, 1], np.int32), (rows, 1))
+    dev = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in
+           (rois, count, pad(np.asarray(scores, F4)), pad(boxes), pad(kps), pad(np.zeros((n, 3), F4)))]
+    out = [torch.full((1,), -7, dtype=torch.int32, device='cuda'), torch.full((K,), -9, dtype=torch.int32, device='cuda'),
+           torch.zeros(K, dtype=torch.float32, device='cuda'), torch.zeros((K, 4), dtype=torch.float64, device='cuda'),
+           torch.zeros((K, 6, 2), dtype=torch.float64, device='cuda'), torch.zeros((K, 3), dtype=torch.float32, device='cuda')]
+    _lib.check(lib.hpe_merge_rois(p(dev[0]), 1, rows, *[p(d) for d in dev[1:]], M, 0, 0, 1, 1, float(F4(iou)), K,
+                                  *[p(o) for o in out], None), 'hpe_merge_rois')
+    torch.cuda.synchronize()
+    kept = int(out[0].cpu()[0])
+    assert 0 <= kept <= K
+    assert (out[1].cpu().numpy()[kept:] == -9).all()
+    return out[1].cpu().numpy()[:kept], out[3].cpu().numpy()[:kept]
+
+
+@pytest.mark.gpu
+def test_gpu_merge_runs_the_same_nms(cases):
+    """Fed a frame's thresholded candidates (float64 boxes, the reference's scores, index order) through
+    the identity remap, hpe_merge_rois must keep what hpe_detect keeps, in the same order: the two
+    callers of the shared sort and greedy pass (csrc/hpe_boxes.h) agree."""
     todo = [('six_frames', f) for f in (0, 3, 4)] + [('flipped', 0), ('zero_area', 0), ('same_box_896', 0),
                                                      ('saturated_high', 0)]
     for name, f in todo:
@@ -384,24 +424,35 @@ def test_gpu_merge_runs_the_same_nms(cases):
         det = gpu_detect([fr], R.logit_threshold(c['t']), c['iou'], c['max_faces'])
         on = R.candidates(fr, c['t'])
         boxes, kps = R.decode(fr['loc'], on)
-        rows, M = 14, 64
-        count = np.asarray([min(max(len(on) - r * M, 0), M) for r in range(rows)], np.int32)
-        pad = lambda a: np.concatenate([a, np.zeros((rows * M - len(on),) + a.shape[1:], a.dtype)])   # noqa: E731
-        rois = np.tile(np.asarray([0, 0, 0, 1, 1], np.int32), (rows, 1))
-        dev = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in
-               (rois, count, pad(R.sigmoid32(fr['cls'][on])), pad(boxes), pad(kps), pad(np.zeros((len(on), 3), F4)))]
-        K = c['max_faces']
-        out = [torch.full((1,), -7, dtype=torch.int32, device='cuda'), torch.full((K,), -9, dtype=torch.int32, device='cuda'),
-               torch.zeros(K, dtype=torch.float32, device='cuda'), torch.zeros((K, 4), dtype=torch.float64, device='cuda'),
-               torch.zeros((K, 6, 2), dtype=torch.float64, device='cuda'), torch.zeros((K, 3), dtype=torch.float32, device='cuda')]
-        _lib.check(lib.hpe_merge_rois(p(dev[0]), 1, rows, *[p(d) for d in dev[1:]], M, 0, 0, 1, 1, float(F4(c['iou'])), K,
-                                      *[p(o) for o in out], None), 'hpe_merge_rois')
-        torch.cuda.synchronize()
-        n = int(out[0].cpu()[0])
+        src, boxes_out = gpu_merge_identity(R.sigmoid32(fr['cls'][on]), boxes, kps, c['iou'], c['max_faces'], 14, 64)
+        n = len(src)
         assert n == int(det['count'][0]), name
-        kept = on[out[1].cpu().numpy()[:n]]
-        np.testing.assert_array_equal(kept, det['det_index'][0, :n], err_msg=name)
-        assert out[3].cpu().numpy()[:n].tobytes() == det['boxes'][0, :n].tobytes(), name
+        np.testing.assert_array_equal(on[src], det['det_index'][0, :n], err_msg=name)
+        assert boxes_out.tobytes() == det['boxes'][0, :n].tobytes(), name
+
+
+@pytest.mark.gpu
+def test_gpu_merge_iou_at_the_threshold(pairs):
+    """test_gpu_detect_iou_at_the_threshold and ..._exact_third for hpe_merge_rois: the two boxes of a
+    pair, decoded as hpe_detect decodes them, go through the identity remap.  With the threshold on the
+    pair's own IoU both are kept, one float32 below it only the first.  (An IoU with the multiply fused
+    into the subtraction fails one of the two for every searched pair.)"""
+    higher, lower = pairs
+    todo = [('higher', R.pair_frame(a, b), 0, 1, ref) for a, b, ref in higher]
+    todo += [('lower', R.pair_frame(a, b), 0, 1, ref) for a, b, ref in lower]
+    todo += [('third', fr, d0, d1, F4(1 / 3)) for fr, d0, d1 in R.exact_third_frames()]
+    failed = []
+    for i, (kind, fr, d0, d1, ref) in enumerate(todo):
+        on = np.asarray([d0, d1])
+        boxes, kps = R.decode(fr['loc'], on)
+        sc = R.sigmoid32(fr['cls'][on])
+        assert sc[0] > sc[1]
+        at = gpu_merge_identity(sc, boxes, kps, ref, 100, 1, 2)[0].tolist()
+        below = gpu_merge_identity(sc, boxes, kps, np.nextafter(ref, F4(0)), 100, 1, 2)[0].tolist()
+        if at != [0, 1] or below != [0]:
+            failed.append((kind, i, float(ref), at, below))
+    print('merge, IoU at the threshold: %d of %d pairs fail' % (len(failed), len(todo)))
+    assert len(todo) >= 19 and not failed, failed
 
 
 # ---- GPU: hpe_gather_features ------------------------------------------------------------------------

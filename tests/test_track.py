@@ -394,6 +394,27 @@ def test_gpu_zero_area_box():
 
 
 @pytest.mark.gpu
+def test_gpu_iou_at_the_threshold():
+    """Box pairs whose IoU a fused multiply-add in the denominator moves by one float32
+    (tests/detect_ref.py's seeded search; tests/test_detect_kernel.py holds on the CPU that it yields
+    them): frame 0 holds the pair's first box, frame 1 its second.  With match_iou on the pair's own IoU
+    frame 1 starts track 1, one float32 below it frame 1 continues track 0; outputs and state equal the
+    restatement bit for bit.  (A contracted IoU fails one of the two for every pair.)"""
+    import detect_ref as R
+    higher, lower = R.iou_pairs()
+    assert len(higher) >= 8 and len(lower) >= 8
+    for kind, group in (('higher', higher), ('lower', lower)):
+        for i, (a, b, ref) in enumerate(group):
+            boxes, _ = R.decode(R.pair_frame(a, b)['loc'], np.arange(2))
+            assert R.iou(boxes[0].astype(np.float32), boxes[1].astype(np.float32)).tobytes() == ref.tobytes()
+            d = _from_boxes([[boxes[0]], [boxes[1]]], 1, seed=11)
+            for thr, ids in ((ref, [0, 1]), (np.nextafter(ref, np.float32(0)), [0, 0])):
+                got = _gpu(1, d, iou=float(thr), K=2)
+                _same(got, _ref(1, d, iou=float(thr), K=2), '%s pair %d at %r' % (kind, i, thr))
+                assert got[0][:, 0].tolist() == ids, (kind, i, float(ref), float(thr), got[0][:, 0].tolist())
+
+
+@pytest.mark.gpu
 def test_gpu_alpha_one_copies():
     d = _walk(9, 4, seed=71, drop=0.1)
     got = _gpu(1, d, alpha=1.0, K=8)

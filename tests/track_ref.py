@@ -3,10 +3,13 @@ must equal bit for bit.
 
 Plain Python over numpy scalars, one rounded operation per expression: float64 for the smoothing
 (state = alpha * m + (1.0 - alpha) * state, hpe.detector.EMAFilter.update), float32 for the IoU on the
-float32 casts of the boxes (oracle.detector_ref._iou, with a non-positive or NaN area giving 0 as
-hpe_merge.hip has it).  The state arrays are updated in place, as the kernel updates them.
+float32 casts of the boxes (tests/detect_ref.py's iou, the one restatement of oracle.detector_ref._iou
+the tests use: a non-positive or NaN area gives 0, as csrc/hpe_boxes.h has it).  The state arrays are
+updated in place, as the kernel updates them.
 """
 import numpy as np
+
+from detect_ref import iou
 
 STATE_D = 23     # HPE_TRACK_STATE_D
 NV = 19          # smoothed values per track: box 4, keypoints 12, pose 3
@@ -20,24 +23,6 @@ def new_state(n_streams, max_tracks):
     si = np.zeros((n_streams, 1 + 2 * K), np.int32)
     si[:, 1:1 + K] = -1
     return si, np.zeros((n_streams, K, STATE_D), F8)
-
-
-def iou(bi, bj):
-    """The detector's IoU on two float32 boxes: corner order agnostic, zero area gives 0."""
-    f = F4
-    with np.errstate(all='ignore'):
-        ymin_i, xmin_i = min(bi[0], bi[2]), min(bi[1], bi[3])
-        ymax_i, xmax_i = max(bi[0], bi[2]), max(bi[1], bi[3])
-        ymin_j, xmin_j = min(bj[0], bj[2]), min(bj[1], bj[3])
-        ymax_j, xmax_j = max(bj[0], bj[2]), max(bj[1], bj[3])
-        area_i = f(f(ymax_i - ymin_i) * f(xmax_i - xmin_i))
-        area_j = f(f(ymax_j - ymin_j) * f(xmax_j - xmin_j))
-        if not (area_i > 0 and area_j > 0):
-            return f(0)
-        iy0, ix0 = max(ymin_i, ymin_j), max(xmin_i, xmin_j)
-        iy1, ix1 = min(ymax_i, ymax_j), min(xmax_i, xmax_j)
-        inter = f(max(f(iy1 - iy0), f(0)) * max(f(ix1 - ix0), f(0)))
-        return f(inter / f(f(area_i + area_j) - inter))
 
 
 def track(n_streams, n_frames, count, boxes, keypoints, poses, alpha, match_iou, max_missed, state_i, state_d,
