@@ -303,3 +303,5 @@ const int* hpe_prog_dwords(const hpe_program* p);
 
 // thread-local error message of the C ABI (hpe_last_error); returns code
 int hpe_fail(int code, const char* fmt, ...);
+// after a kernel launch by entry point `fn`: HPE_OK, or the launch error as "<fn> launch: <hip error string>"
+int hpe_launched(const char* fn);

@@ -149,9 +149,7 @@ extern "C" int hpe_detect(const float* cls0, const float* cls1, const float* loc
   DetArgs a = {cls0, cls1, loc0, loc1, pose0, pose1, score_logit_threshold, iou_threshold, (int)max_faces,
                count, det_index, scores, boxes, keypoints, poses};
   hipLaunchKernelGGL(detect_kernel, dim3((unsigned)n_images), dim3(DET_T), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_detect launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return hpe_launched("hpe_detect");
 }
 
 // ---- feature-dataset extraction ------------------------------------------------
@@ -196,7 +194,5 @@ extern "C" int hpe_gather_features(const int32_t* count, const int32_t* det_inde
   if (n_images * k > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_gather_features: batch too large");
   hipLaunchKernelGGL(gather_features_kernel, dim3((unsigned)(n_images * k)), dim3(64), 0, (hipStream_t)stream,
                      count, det_index, (int)max_faces, (int)k, tap0, (int)c0, tap1, (int)c1, feat0, feat1, src);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_gather_features launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return hpe_launched("hpe_gather_features");
 }

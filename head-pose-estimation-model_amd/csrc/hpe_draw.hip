@@ -298,12 +298,6 @@ __global__ void __launch_bounds__(256) pose_prims_kernel(PosePrimArgs a) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-static int draw_launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s launch: %s", fn, hipGetErrorString(e));
-  return HPE_OK;
-}
-
 // (n - 1) * frame_stride + (rows - 1) * row_stride + row_bytes must fit int64
 static bool draw_extent_ok(int64_t n, int64_t frame_stride, int64_t rows, int64_t row_stride, int64_t row_bytes) {
   int64_t a, b, s;
@@ -349,7 +343,7 @@ extern "C" int hpe_draw(uint8_t* frames, int64_t n_frames, int32_t h, int32_t w,
                       n_colours};
   hipLaunchKernelGGL(draw_kernel<false>, dim3((unsigned)(n_frames * tx * ty)), dim3(DRAW_T), 0, (hipStream_t)stream,
                      a);
-  return draw_launched("hpe_draw");
+  return hpe_launched("hpe_draw");
 }
 
 extern "C" int hpe_draw_nv12(uint8_t* y, uint8_t* uv, int64_t n_frames, int32_t h, int32_t w, int64_t y_row_stride,
@@ -371,7 +365,7 @@ extern "C" int hpe_draw_nv12(uint8_t* y, uint8_t* uv, int64_t n_frames, int32_t 
                       n_prims, P, colours, n_colours};
   hipLaunchKernelGGL(draw_kernel<true>, dim3((unsigned)(n_frames * tx * ty)), dim3(DRAW_T), 0, (hipStream_t)stream,
                      a);
-  return draw_launched("hpe_draw_nv12");
+  return hpe_launched("hpe_draw_nv12");
 }
 
 extern "C" int hpe_pose_prims(const int32_t* count, const double* boxes, const double* keypoints, const float* poses,
@@ -399,5 +393,5 @@ extern "C" int hpe_pose_prims(const int32_t* count, const double* boxes, const d
   const PosePrimArgs a = {count, boxes, keypoints, poses, total, max_faces, src_x0, src_y0, (double)src_w,
                           (double)src_h, box_th, kp_radius, {axis_th_x, axis_th_y, axis_th_z}, prims, n_prims};
   hipLaunchKernelGGL(pose_prims_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return draw_launched("hpe_pose_prims");
+  return hpe_launched("hpe_pose_prims");
 }

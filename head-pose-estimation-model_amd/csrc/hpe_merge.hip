@@ -161,7 +161,5 @@ extern "C" int hpe_merge_rois(const int32_t* rois, int64_t n_frames, int32_t row
       hipSuccess)
     return hpe_fail(HPE_ERUNTIME, "hpe_merge_rois: LDS attribute");
   hipLaunchKernelGGL(merge_rois_kernel, dim3((unsigned)n_frames), dim3(MRG_T), lds, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_merge_rois launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return hpe_launched("hpe_merge_rois");
 }

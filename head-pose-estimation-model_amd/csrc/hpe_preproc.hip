@@ -12,13 +12,20 @@
 // the filter passes, the NV12 conversion and hpe_face_rois' float64 need it), so no multiply-add pair
 // becomes an FMA (the only fused ops left are inside the division expansions).
 // One thread per output pixel (three channels), lanes along x; a gather bounded by load latency.
-// Two kernels around one body: preprocess_kernel (one crop for the batch) and preprocess_rois_kernel
-// (one row of a device table of regions of interest per output, which may reach outside the frame)
-// differ in where the tap geometry comes from and in the gather; the table, the pixel decode, the row
-// load, the two filter passes and the store exist once.  preprocess_nv12_kernel and
-// preprocess_rois_nv12_kernel are the same two around a gather that reads decoded NV12 video frames
-// and converts each tap to B, G, R bytes (hpe_preprocess_nv12, hpe_preprocess_rois_nv12).  Last: the
-// table of a second detector pass (hpe_face_rois).
+// One kernel template, preprocess_kernel<Src, ROIS>, with two compile-time axes and four instantiations:
+//   ROIS: where an output's rectangle comes from.  false: one crop for the batch, its scale computed
+//     on the host.  true: one row of a device table of regions of interest per output, which may reach
+//     outside the frame; this adds the row's validity test with its pad-constant exit, the per-row
+//     scale and the in-frame tests of the window and of each tap.
+//   Src: where the bytes come from.  BgrSrc: packed 3-byte pixels in either channel order.  Nv12Src:
+//     decoded NV12 video frames, each tap converted to B, G, R bytes in the gather.  A source gives
+//     frame i, the interior 4 x 4 window, and the taps one by one under an in-frame mask: Nv12Src for
+//     the window as a whole (its tap rows share chroma loads), BgrSrc row by row, from one small
+//     gather per form in the kernel's body (see by_row there for why).
+// The body names no pixel format and exists once; the four C entry points (hpe_preprocess,
+// hpe_preprocess_rois, hpe_preprocess_nv12, hpe_preprocess_rois_nv12) check their arguments, fill a
+// source and a geometry struct and share one launch helper.  Last: the table of a second detector pass
+// (hpe_face_rois).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,14 +40,17 @@
 
 typedef uint32_t u32u __attribute__((aligned(1)));   // a dword at any byte address
 
-struct PreArgs {           // filled by hpe_preprocess in this order, one line there per line here
-  const uint8_t* frames;   // + crop origin of frame 0
+// the outputs and their rectangles.  A specialization reads the fields of its own ROIS value only; each
+// form's fields lie together, so that they arrive in a few wide scalar loads at the kernel's start.
+struct Geom {
   float* out;
-  int64_t frame_stride, row_stride;   // bytes
-  int crop_w, crop_h, out_w, out_h;
-  int total;               // n * out_h * out_w
-  int bgr;
-  float sx, sy;            // (float)crop_w / (float)out_w, (float)crop_h / (float)out_h
+  const int32_t* rois;     // ROIS true: output r is row r of this (m, 5) table: frame, x0, y0, w, h
+  int out_w, out_h;
+  int total;               // outputs * out_h * out_w
+  int n_frames, in_w, in_h;
+  int pad[3];              // pad bytes in the source's channel order
+  int x0, y0, w, h;        // ROIS false: one crop for the batch
+  float sx, sy;            // (float)w / (float)out_w, (float)h / (float)out_h
 };
 
 // TF's coefficient table entries [i * 2] and [i * 2 + 1] at t = i / 1024 (exact in fp32)
@@ -81,7 +91,7 @@ __device__ __forceinline__ void taps(int o, float scale, int limit, int* idx, fl
   }
 }
 
-// ---- the body preprocess_kernel and preprocess_rois_kernel share: everything but the gather ------
+// ---- what the kernel is made of, apart from the gather -------------------------------------------
 // byte -> (float)(byte / 255.0), the reference's float64 division
 __device__ __forceinline__ void fill_lut(float* lut) {
   lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);
@@ -147,114 +157,34 @@ __device__ __forceinline__ void filter_store(const float* lut, const uint8_t (*b
   store_px(dst, o, bgr);
 }
 
-__global__ void __launch_bounds__(PRE_T) preprocess_kernel(PreArgs a) {
-  __shared__ float lut[256];
-  fill_lut(lut);
-  Px p;
-  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
-
-  int yi[4], xi[4];
-  float wy[4], wx[4];
-  taps(p.oy, a.sy, a.crop_h, yi, wy);
-  taps(p.ox, a.sx, a.crop_w, xi, wx);
-  // no x tap clamped: the four taps of a row are 12 contiguous bytes
-  const bool interior = xi[3] - xi[0] == 3;
-
-  const uint8_t* base = a.frames + p.img * a.frame_stride;
-  uint8_t b[4][12];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint8_t* r = base + (int64_t)yi[j] * a.row_stride;
-    if (interior) {
-      load12(r + xi[0] * 3, b[j]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) load3(r + xi[k] * 3, b[j] + 3 * k);
-    }
-  }
-  filter_store(lut, b, wy, wx, a.bgr, a.out + (int64_t)p.pix * 3);
-}
-
-// ---- per-row regions of interest ------------------------------------------------------------------
-// hpe_preprocess_rois: output r is hpe_preprocess of a whole h x w canvas whose pixel (y, x) is the
-// frame's pixel (y0 + y, x0 + x) where that lies inside the frame and the pad bytes elsewhere, for row
-// r = (frame, x0, y0, w, h) of a device table.  The kernel is the shared body around its own gather
-// (taps clamp to the canvas, not to the frame), so an ROI inside the frame equals hpe_preprocess with
-// that crop and an ROI reaching outside equals hpe_preprocess on a host-padded copy, bit for bit.
-// A row's rectangle must pass roi_rect_ok (hpe_boxes.h): every coordinate sum below then fits int32.
-
-struct RoiArgs {           // filled by hpe_preprocess_rois in this order, one line there per line here
+// ---- packed BGR (or RGB) frames ------------------------------------------------------------------
+struct BgrSrc {
   const uint8_t* frames;
-  const int32_t* rois;     // (m, 5): frame, x0, y0, w, h
-  float* out;
   int64_t frame_stride, row_stride;   // bytes
-  int n_frames, in_w, in_h, out_w, out_h;
-  int total;               // m * out_h * out_w
   int bgr;
-  int pad0, pad1, pad2;    // pad bytes in the frame's channel order
+
+  // The tap rows are independent, so this source gathers row by row, from loops that stand in the
+  // kernel's body.  With the same loops inside window() / tap_by_tap() members as Nv12Src has them,
+  // the compiler keeps the 48 window bytes packed four to a register and packs and unpacks them around
+  // every tap: 1,380 instead of 985 instructions in the ROI form, and 10 to 16 % more time on MI355X.
+  static constexpr bool by_row = true;
+  // hpe_preprocess folds the crop's origin into `frames`, which saves the crop form a register; an
+  // NV12 tap's chroma pair depends on its frame coordinates' parity, so Nv12Src cannot do the same
+  static constexpr bool origin_in_frame = true;
+
+  __device__ __forceinline__ int order() const { return bgr; }
+  __device__ __forceinline__ const uint8_t* frame(int64_t i) const { return frames + i * frame_stride; }
+  __device__ __forceinline__ const uint8_t* row(const uint8_t* f, int y) const { return f + (int64_t)y * row_stride; }
+  // columns x0 .. x0 + 3 of a row, all inside the frame: 12 contiguous bytes
+  __device__ __forceinline__ void row_window(const uint8_t* r, int x0, uint8_t* b) const { load12(r + x0 * 3, b); }
+  __device__ __forceinline__ void tap(const uint8_t* r, int x, uint8_t* b) const { load3(r + x * 3, b); }
 };
 
-__global__ void __launch_bounds__(PRE_T) preprocess_rois_kernel(RoiArgs a) {
-  __shared__ float lut[256];
-  fill_lut(lut);
-  Px p;   // p.img: the ROI row
-  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
-
-  const int32_t* roi = a.rois + p.img * 5;
-  const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
-  float* dst = a.out + (int64_t)p.pix * 3;
-  const uint8_t pad[3] = {(uint8_t)a.pad0, (uint8_t)a.pad1, (uint8_t)a.pad2};
-  const bool valid = fr >= 0 && fr < a.n_frames && roi_rect_ok(x0, y0, cw, ch);
-  if (!valid) {   // reads no frame memory
-    float o[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
-    store_px(dst, o, a.bgr);
-    return;
-  }
-
-  int yi[4], xi[4];
-  float wy[4], wx[4];
-  taps(p.oy, (float)ch / (float)a.out_h, ch, yi, wy);
-  taps(p.ox, (float)cw / (float)a.out_w, cw, xi, wx);
-  // frame coordinates of the taps (ascending along each axis, as the clamped canvas indices are)
-  int fy[4], fx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    fy[k] = y0 + yi[k];
-    fx[k] = x0 + xi[k];
-  }
-  const bool x_in = fx[0] >= 0 && fx[3] < a.in_w;
-  const bool y_in = fy[0] >= 0 && fy[3] < a.in_h;
-  // the whole 4 x 4 window inside the frame and no x tap clamped: 12 contiguous bytes per row
-  const bool interior = x_in && y_in && xi[3] - xi[0] == 3;
-
-  const uint8_t* base = a.frames + (int64_t)fr * a.frame_stride;
-  uint8_t b[4][12];
-  if (interior) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) load12(base + (int64_t)fy[j] * a.row_stride + fx[0] * 3, b[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool row_in = fy[j] >= 0 && fy[j] < a.in_h;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (row_in && fx[k] >= 0 && fx[k] < a.in_w)
-          load3(base + (int64_t)fy[j] * a.row_stride + fx[k] * 3, b[j] + 3 * k);
-        else
-          load3(pad, b[j] + 3 * k);
-      }
-    }
-  }
-  filter_store(lut, b, wy, wx, a.bgr, dst);
-}
-
 // ---- NV12 frames ------------------------------------------------------------------------------------
-// hpe_preprocess_nv12 / hpe_preprocess_rois_nv12: the two kernels above with a gather that reads a
-// luma plane and a half-resolution plane of interleaved (U, V) pairs and fills b[][] with the B, G, R
-// bytes it converts per tap (include/hpe.h states the rule; tests/nv12_ref.py restates it), so the
-// output equals the BGR kernel's on the converted frame, bit for bit.  The chroma of pixel (y, x) is the
+// Nv12Src (hpe_preprocess_nv12 / hpe_preprocess_rois_nv12): a gather that reads a luma plane and a
+// half-resolution plane of interleaved (U, V) pairs and fills b[][] with the B, G, R bytes it converts
+// per tap (include/hpe.h states the rule; tests/nv12_ref.py restates it), so the output equals
+// BgrSrc's on the converted frame, bit for bit.  The chroma of pixel (y, x) is the
 // pair (y >> 1, x >> 1): a 4 x 4 window touches at most 3 chroma rows x 3 pairs.  The interior path
 // loads one dword of luma per tap row and each distinct pair once, all before the first conversion,
 // and computes a pair's three chroma terms once; no load touches a byte past in_w in a row.
@@ -369,120 +299,165 @@ __device__ __forceinline__ void nv12_taps(const Nv12Frame& f, const Nv12Coef& k,
   }
 }
 
-struct PreNv12Args {       // filled by hpe_preprocess_nv12 in this order, one line there per line here
-  const uint8_t *y, *uv;   // frame 0
-  float* out;
-  int64_t y_frame, y_row, uv_frame, uv_row;   // bytes
-  int crop_x0, crop_y0, crop_w, crop_h, out_w, out_h;
-  int total;               // n * out_h * out_w
-  int matrix;
-  float sx, sy;            // (float)crop_w / (float)out_w, (float)crop_h / (float)out_h
-};
-
-__global__ void __launch_bounds__(PRE_T) preprocess_nv12_kernel(PreNv12Args a) {
-  __shared__ float lut[256];
-  fill_lut(lut);
-  Px p;
-  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
-
-  int yi[4], xi[4];
-  float wy[4], wx[4];
-  taps(p.oy, a.sy, a.crop_h, yi, wy);
-  taps(p.ox, a.sx, a.crop_w, xi, wx);
-  // frame coordinates: the chroma sample depends on their parity
-  int fy[4], fx[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    fy[k] = a.crop_y0 + yi[k];
-    fx[k] = a.crop_x0 + xi[k];
-  }
-  const Nv12Coef coef = nv12_coef(a.matrix);
-  const Nv12Frame f = {a.y + p.img * a.y_frame, a.uv + p.img * a.uv_frame, a.y_row, a.uv_row};
-  uint8_t b[4][12];
-  if (xi[3] - xi[0] == 3) {   // no x tap clamped
-    nv12_window(f, coef, fy, fx[0], b);
-  } else {
-    const bool in[4][4] = {{true, true, true, true}, {true, true, true, true}, {true, true, true, true},
-                           {true, true, true, true}};
-    nv12_taps(f, coef, fy, fx, in, nullptr, b);
-  }
-  filter_store(lut, b, wy, wx, 1, a.out + (int64_t)p.pix * 3);
-}
-
-struct RoiNv12Args {       // filled by hpe_preprocess_rois_nv12 in this order, one line there per line here
+struct Nv12Src {
   const uint8_t *y, *uv;
-  const int32_t* rois;     // (m, 5): frame, x0, y0, w, h
-  float* out;
   int64_t y_frame, y_row, uv_frame, uv_row;   // bytes
-  int n_frames, in_w, in_h, out_w, out_h;
-  int total;               // m * out_h * out_w
   int matrix;
-  int pad_b, pad_g, pad_r;
+
+  static constexpr bool by_row = false;            // the tap rows share their chroma loads
+  static constexpr bool origin_in_frame = false;
+
+  __device__ __forceinline__ int order() const { return 1; }   // the conversion makes B, G, R
+  __device__ __forceinline__ Nv12Frame frame(int64_t i) const {
+    return {y + i * y_frame, uv + i * uv_frame, y_row, uv_row};
+  }
+  __device__ __forceinline__ void window(const Nv12Frame& f, const int* fy, int fx0, uint8_t (*b)[12]) const {
+    nv12_window(f, nv12_coef(matrix), fy, fx0, b);
+  }
+  __device__ __forceinline__ void tap_by_tap(const Nv12Frame& f, const int* fy, const int* fx, const bool (*in)[4],
+                                             const uint8_t* pad, uint8_t (*b)[12]) const {
+    nv12_taps(f, nv12_coef(matrix), fy, fx, in, pad, b);
+  }
 };
 
-__global__ void __launch_bounds__(PRE_T) preprocess_rois_nv12_kernel(RoiNv12Args a) {
+// ---- the kernel ------------------------------------------------------------------------------------
+// ROIS false: output i is the crop (x0, y0, w, h) of frame i.  ROIS true: output r is the same
+// preparation of a whole h x w canvas whose pixel (y, x) is the frame's pixel (y0 + y, x0 + x) where that
+// lies inside the frame and the pad bytes elsewhere, for row r = (frame, x0, y0, w, h) of the table.  The
+// taps clamp to the rectangle, not to the frame, so an ROI inside the frame equals the crop form with
+// that crop and an ROI reaching outside equals the crop form on a host-padded copy, bit for bit.  A
+// row's rectangle must pass roi_rect_ok (hpe_boxes.h): every coordinate sum below then fits int32.
+template <class Src, bool ROIS>
+__global__ void __launch_bounds__(PRE_T) preprocess_kernel(Src src, Geom g) {
   __shared__ float lut[256];
   fill_lut(lut);
-  Px p;   // p.img: the ROI row
-  if (!decode_px(a.total, a.out_w, a.out_h, &p)) return;
+  Px p;   // p.img: the frame, or the ROI row
+  if (!decode_px(g.total, g.out_w, g.out_h, &p)) return;
+  float* dst = g.out + (int64_t)p.pix * 3;
 
-  const int32_t* roi = a.rois + p.img * 5;
-  const int fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
-  float* dst = a.out + (int64_t)p.pix * 3;
-  const uint8_t pad[3] = {(uint8_t)a.pad_b, (uint8_t)a.pad_g, (uint8_t)a.pad_r};
-  const bool valid = fr >= 0 && fr < a.n_frames && roi_rect_ok(x0, y0, cw, ch);
-  if (!valid) {   // reads no frame memory
-    float o[3];
+  int64_t fr = p.img;
+  int x0 = g.x0, y0 = g.y0, cw = g.w, ch = g.h;
+  float sx = g.sx, sy = g.sy;
+  uint8_t pad[3] = {0, 0, 0};
+  int in_w = 0, in_h = 0;   // the frame's size, read here with the rest of the ROI form's fields
+  if constexpr (ROIS) {
+    in_w = g.in_w, in_h = g.in_h;
+    const int32_t* roi = g.rois + p.img * 5;
+    fr = roi[0], x0 = roi[1], y0 = roi[2], cw = roi[3], ch = roi[4];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
-    store_px(dst, o, 1);
-    return;
+    for (int c = 0; c < 3; ++c) pad[c] = (uint8_t)g.pad[c];
+    if (!(fr >= 0 && fr < g.n_frames && roi_rect_ok(x0, y0, cw, ch))) {   // invalid: reads no frame memory
+      float o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c] = (lut[pad[c]] - 0.5f) / 0.5f;
+      store_px(dst, o, src.order());
+      return;
+    }
+    sx = (float)cw / (float)g.out_w;
+    sy = (float)ch / (float)g.out_h;
   }
 
   int yi[4], xi[4];
   float wy[4], wx[4];
-  taps(p.oy, (float)ch / (float)a.out_h, ch, yi, wy);
-  taps(p.ox, (float)cw / (float)a.out_w, cw, xi, wx);
+  taps(p.oy, sy, ch, yi, wy);
+  taps(p.ox, sx, cw, xi, wx);
+  // frame coordinates of the taps (ascending along each axis, as the clamped indices are); a crop whose
+  // origin the host folded into the frame pointer counts from that origin
+  if constexpr (!ROIS && Src::origin_in_frame) x0 = y0 = 0;
   int fy[4], fx[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     fy[k] = y0 + yi[k];
     fx[k] = x0 + xi[k];
   }
-  const bool x_in = fx[0] >= 0 && fx[3] < a.in_w;
-  const bool y_in = fy[0] >= 0 && fy[3] < a.in_h;
-  const Nv12Coef coef = nv12_coef(a.matrix);
-  const Nv12Frame f = {a.y + (int64_t)fr * a.y_frame, a.uv + (int64_t)fr * a.uv_frame, a.y_row, a.uv_row};
+  // no x tap clamped and, for an ROI, the whole 4 x 4 window inside the frame
+  bool interior = xi[3] - xi[0] == 3;
+  if constexpr (ROIS) interior = interior && fx[0] >= 0 && fx[3] < in_w && fy[0] >= 0 && fy[3] < in_h;
+
+  const auto f = src.frame(fr);
   uint8_t b[4][12];
-  if (x_in && y_in && xi[3] - xi[0] == 3) {   // the whole window inside the frame and no x tap clamped
-    nv12_window(f, coef, fy, fx[0], b);
-  } else {
-    bool in[4][4];
+  if constexpr (Src::by_row && !ROIS) {
+    // a crop lies inside its frame; the branch stands in the row loop (66 VGPRs; around it, 74 and a
+    // wave per SIMD less)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bool row_in = fy[j] >= 0 && fy[j] < a.in_h;
+      const auto r = src.row(f, fy[j]);
+      if (interior) {
+        src.row_window(r, fx[0], b[j]);
+      } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) in[j][k] = row_in && fx[k] >= 0 && fx[k] < a.in_w;
+        for (int k = 0; k < 4; ++k) src.tap(r, fx[k], b[j] + 3 * k);
+      }
     }
-    nv12_taps(f, coef, fy, fx, in, pad, b);
+  } else if constexpr (Src::by_row) {
+    // an ROI: the branch stands around the row loop, so that the four rows' loads go out together (in
+    // it, 8 % slower on MI355X); a tap outside the frame takes the pad bytes
+    if (interior) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) src.row_window(src.row(f, fy[j]), fx[0], b[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool row_in = fy[j] >= 0 && fy[j] < in_h;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (row_in && fx[k] >= 0 && fx[k] < in_w)
+            src.tap(src.row(f, fy[j]), fx[k], b[j] + 3 * k);
+          else
+            load3(pad, b[j] + 3 * k);
+        }
+      }
+    }
+  } else if (interior) {
+    src.window(f, fy, fx[0], b);
+  } else {
+    bool in[4][4];   // which taps lie in the frame; a crop lies inside it: all true at compile time
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool row_in = !ROIS || (fy[j] >= 0 && fy[j] < in_h);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) in[j][k] = row_in && (!ROIS || (fx[k] >= 0 && fx[k] < in_w));
+    }
+    src.tap_by_tap(f, fy, fx, in, pad, b);
   }
-  filter_store(lut, b, wy, wx, 1, dst);
+  filter_store(lut, b, wy, wx, src.order(), dst);
 }
 
-// what hpe_preprocess and hpe_preprocess_rois check of the frames and the output size, in the order
-// their callers see; crop: hpe_preprocess's (x0, y0, w, h), null for hpe_preprocess_rois
-static int check_frames(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
-                        const int32_t* crop, int32_t out_h, int32_t out_w) {
-  if (crop && (in_h <= 0 || in_w <= 0 || crop[2] <= 0 || crop[3] <= 0 || out_h <= 0 || out_w <= 0))
-    return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, crop %d x %d, out %d x %d)", fn, in_h,
-                    in_w, crop[3], crop[2], out_h, out_w);
+// ---- the C entry points ------------------------------------------------------------------------------
+// what the four check alike, in the order their callers see.  crop: the crop forms' (x0, y0, w, h),
+// null for the ROI forms
+static int check_rect(const char* fn, int32_t in_h, int32_t in_w, const int32_t* crop, int32_t out_h,
+                      int32_t out_w) {
   if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
     return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, out %d x %d)", fn, in_h, in_w, out_h,
                     out_w);
-  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "%s: frame width %d too large", fn, in_w);
-  if (crop && (crop[0] < 0 || crop[1] < 0 || (int64_t)crop[0] + crop[2] > in_w || (int64_t)crop[1] + crop[3] > in_h))
+  if (!crop) return HPE_OK;
+  if (crop[2] <= 0 || crop[3] <= 0)
+    return hpe_fail(HPE_EINVAL, "%s: crop sizes must be positive (%d x %d)", fn, crop[3], crop[2]);
+  if (crop[0] < 0 || crop[1] < 0 || (int64_t)crop[0] + crop[2] > in_w || (int64_t)crop[1] + crop[3] > in_h)
     return hpe_fail(HPE_EINVAL, "%s: crop (%d, %d, %d, %d) outside the %d x %d frame", fn, crop[0], crop[1], crop[2],
                     crop[3], in_w, in_h);
+  return HPE_OK;
+}
+
+// the ROI forms: the frame count must fit the kernel's int, the pad bytes a byte
+static int check_table(const char* fn, int64_t n_frames, int32_t pad0, int32_t pad1, int32_t pad2) {
+  if (n_frames > 0x7fffffff) return hpe_fail(HPE_EINVAL, "%s: batch too large", fn);
+  if (pad0 < 0 || pad0 > 255 || pad1 < 0 || pad1 > 255 || pad2 < 0 || pad2 > 255)
+    return hpe_fail(HPE_EINVAL, "%s: pad bytes (%d, %d, %d) outside 0..255", fn, pad0, pad1, pad2);
+  return HPE_OK;
+}
+
+// count (`what`: its name in the message) outputs of out_h x out_w pixels must fit the kernel's int index
+static int check_count(const char* fn, const char* what, int64_t count, int32_t out_h, int32_t out_w) {
+  if (count > 0 && count > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
+    return hpe_fail(HPE_EINVAL, "%s: %s * out_h * out_w exceeds INT32_MAX", fn, what);
+  return HPE_OK;
+}
+
+// a packed source: one row stride in bytes, the frames back to back
+static int check_bgr(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes) {
+  if (in_w > 0x7fffffff / 3) return hpe_fail(HPE_EINVAL, "%s: frame width %d too large", fn, in_w);
   if (row_stride_bytes < 3 * (int64_t)in_w)
     return hpe_fail(HPE_EINVAL, "%s: row stride %lld below 3 * in_w = %lld", fn, (long long)row_stride_bytes,
                     3 * (long long)in_w);
@@ -491,21 +466,12 @@ static int check_frames(const char* fn, int64_t n, int32_t in_h, int32_t in_w, i
   return HPE_OK;
 }
 
-// the same for the NV12 entry points: two planes, each with a row and a frame stride in bytes
+// an NV12 source: two planes, each with a row and a frame stride in bytes
 static int check_nv12(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int64_t y_row, int64_t y_frame,
-                      int64_t uv_row, int64_t uv_frame, int32_t matrix, const int32_t* crop, int32_t out_h,
-                      int32_t out_w) {
-  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0)
-    return hpe_fail(HPE_EINVAL, "%s: sizes must be positive (frame %d x %d, out %d x %d)", fn, in_h, in_w, out_h,
-                    out_w);
-  if (crop && (crop[2] <= 0 || crop[3] <= 0))
-    return hpe_fail(HPE_EINVAL, "%s: crop sizes must be positive (%d x %d)", fn, crop[3], crop[2]);
+                      int64_t uv_row, int64_t uv_frame, int32_t matrix) {
   if ((in_h | in_w) & 1) return hpe_fail(HPE_EINVAL, "%s: an NV12 frame's size %d x %d must be even", fn, in_h, in_w);
   if (matrix != 0 && matrix != 1)
     return hpe_fail(HPE_EINVAL, "%s: matrix %d is neither 0 (BT.601) nor 1 (BT.709)", fn, matrix);
-  if (crop && (crop[0] < 0 || crop[1] < 0 || (int64_t)crop[0] + crop[2] > in_w || (int64_t)crop[1] + crop[3] > in_h))
-    return hpe_fail(HPE_EINVAL, "%s: crop (%d, %d, %d, %d) outside the %d x %d frame", fn, crop[0], crop[1], crop[2],
-                    crop[3], in_w, in_h);
   if (y_row < in_w || uv_row < in_w)
     return hpe_fail(HPE_EINVAL, "%s: row strides (%lld, %lld) below in_w = %d", fn, (long long)y_row,
                     (long long)uv_row, in_w);
@@ -518,65 +484,59 @@ static int check_nv12(const char* fn, int64_t n, int32_t in_h, int32_t in_w, int
   return HPE_OK;
 }
 
-// count (`what`: its name in the message) outputs of out_h x out_w pixels must fit the kernels' int index
-static int check_count(const char* fn, const char* what, int64_t count, int32_t out_h, int32_t out_w) {
-  if (count > 0 && count > (int64_t)0x7fffffff / ((int64_t)out_h * out_w))
-    return hpe_fail(HPE_EINVAL, "%s: %s * out_h * out_w exceeds INT32_MAX", fn, what);
-  return HPE_OK;
+static Geom crop_geom(float* out, int64_t n, int32_t out_h, int32_t out_w, const int32_t* crop) {
+  return {.out = out, .out_w = out_w, .out_h = out_h, .total = (int)(n * out_h * out_w),
+          .x0 = crop[0], .y0 = crop[1], .w = crop[2], .h = crop[3],
+          .sx = (float)crop[2] / (float)out_w, .sy = (float)crop[3] / (float)out_h};
 }
 
-static unsigned pre_grid(int total) { return (unsigned)(((int64_t)total + PRE_T - 1) / PRE_T); }
+static Geom rois_geom(float* out, int64_t m, int32_t out_h, int32_t out_w, const int32_t* rois, int64_t n_frames,
+                      int32_t in_h, int32_t in_w, int32_t pad0, int32_t pad1, int32_t pad2) {
+  return {.out = out, .rois = rois, .out_w = out_w, .out_h = out_h, .total = (int)(m * out_h * out_w),
+          .n_frames = (int)n_frames, .in_w = in_w, .in_h = in_h, .pad = {pad0, pad1, pad2}};
+}
 
-static int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s launch: %s", fn, hipGetErrorString(e));
-  return HPE_OK;
+template <class Src, bool ROIS>
+static int launch(const char* fn, const Src& src, const Geom& g, void* stream) {
+  const unsigned grid = (unsigned)(((int64_t)g.total + PRE_T - 1) / PRE_T);
+  hipLaunchKernelGGL((preprocess_kernel<Src, ROIS>), dim3(grid), dim3(PRE_T), 0, (hipStream_t)stream, src, g);
+  return hpe_launched(fn);
 }
 
 extern "C" int hpe_preprocess(const uint8_t* frames, int64_t n, int32_t in_h, int32_t in_w, int64_t row_stride_bytes,
                               int32_t crop_x0, int32_t crop_y0, int32_t crop_w, int32_t crop_h, int32_t bgr,
                               float* out, int32_t out_h, int32_t out_w, void* stream) {
-  if (n < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess: negative frame count");
+  const char* fn = "hpe_preprocess";
+  if (n < 0) return hpe_fail(HPE_EINVAL, "%s: negative frame count", fn);
   const int32_t crop[4] = {crop_x0, crop_y0, crop_w, crop_h};
-  if (int rc = check_frames("hpe_preprocess", n, in_h, in_w, row_stride_bytes, crop, out_h, out_w)) return rc;
-  if (int rc = check_count("hpe_preprocess", "n", n, out_h, out_w)) return rc;
+  if (int rc = check_rect(fn, in_h, in_w, crop, out_h, out_w)) return rc;
+  if (int rc = check_bgr(fn, n, in_h, in_w, row_stride_bytes)) return rc;
+  if (int rc = check_count(fn, "n", n, out_h, out_w)) return rc;
   if (n == 0) return HPE_OK;
-  if (!frames || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess: null argument");
-  const PreArgs a = {frames + (int64_t)crop_y0 * row_stride_bytes + (int64_t)crop_x0 * 3,
-                     out,
-                     (int64_t)in_h * row_stride_bytes, row_stride_bytes,
-                     crop_w, crop_h, out_w, out_h,
-                     (int)(n * out_h * out_w),
-                     bgr,
-                     (float)crop_w / (float)out_w, (float)crop_h / (float)out_h};
-  hipLaunchKernelGGL(preprocess_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  return launched("hpe_preprocess");
+  if (!frames || !out) return hpe_fail(HPE_EINVAL, "%s: null argument", fn);
+  const BgrSrc src = {.frames = frames + (int64_t)crop_y0 * row_stride_bytes + (int64_t)crop_x0 * 3,   // origin_in_frame
+                      .frame_stride = (int64_t)in_h * row_stride_bytes,
+                      .row_stride = row_stride_bytes, .bgr = bgr};
+  return launch<BgrSrc, false>(fn, src, crop_geom(out, n, out_h, out_w, crop), stream);
 }
 
 extern "C" int hpe_preprocess_rois(const uint8_t* frames, int64_t n_frames, int32_t in_h, int32_t in_w,
                                    int64_t row_stride_bytes, const int32_t* rois, int64_t m, int32_t pad_b0,
                                    int32_t pad_b1, int32_t pad_b2, int32_t bgr, float* out, int32_t out_h,
                                    int32_t out_w, void* stream) {
-  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: negative frame or ROI count");
-  if (int rc = check_frames("hpe_preprocess_rois", n_frames, in_h, in_w, row_stride_bytes, nullptr, out_h, out_w))
-    return rc;
-  if (n_frames > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: batch too large");
-  if (pad_b0 < 0 || pad_b0 > 255 || pad_b1 < 0 || pad_b1 > 255 || pad_b2 < 0 || pad_b2 > 255)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: pad bytes (%d, %d, %d) outside 0..255", pad_b0, pad_b1, pad_b2);
-  if (int rc = check_count("hpe_preprocess_rois", "m", m, out_h, out_w)) return rc;
+  const char* fn = "hpe_preprocess_rois";
+  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "%s: negative frame or ROI count", fn);
+  if (int rc = check_rect(fn, in_h, in_w, nullptr, out_h, out_w)) return rc;
+  if (int rc = check_bgr(fn, n_frames, in_h, in_w, row_stride_bytes)) return rc;
+  if (int rc = check_table(fn, n_frames, pad_b0, pad_b1, pad_b2)) return rc;
+  if (int rc = check_count(fn, "m", m, out_h, out_w)) return rc;
   if (m == 0) return HPE_OK;
   // without frames every row is invalid and nothing is read through `frames`
-  if ((!frames && n_frames > 0) || !rois || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois: null argument");
-  const RoiArgs a = {frames,
-                     rois,
-                     out,
-                     (int64_t)in_h * row_stride_bytes, row_stride_bytes,
-                     (int)n_frames, in_w, in_h, out_w, out_h,
-                     (int)(m * out_h * out_w),
-                     bgr,
-                     pad_b0, pad_b1, pad_b2};
-  hipLaunchKernelGGL(preprocess_rois_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  return launched("hpe_preprocess_rois");
+  if ((!frames && n_frames > 0) || !rois || !out) return hpe_fail(HPE_EINVAL, "%s: null argument", fn);
+  const BgrSrc src = {.frames = frames, .frame_stride = (int64_t)in_h * row_stride_bytes,
+                      .row_stride = row_stride_bytes, .bgr = bgr};
+  return launch<BgrSrc, true>(
+      fn, src, rois_geom(out, m, out_h, out_w, rois, n_frames, in_h, in_w, pad_b0, pad_b1, pad_b2), stream);
 }
 
 extern "C" int hpe_preprocess_nv12(const uint8_t* y, const uint8_t* uv, int64_t n, int32_t in_h, int32_t in_w,
@@ -584,23 +544,18 @@ extern "C" int hpe_preprocess_nv12(const uint8_t* y, const uint8_t* uv, int64_t 
                                    int64_t uv_frame_stride, int32_t matrix, int32_t crop_x0, int32_t crop_y0,
                                    int32_t crop_w, int32_t crop_h, float* out, int32_t out_h, int32_t out_w,
                                    void* stream) {
-  if (n < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_nv12: negative frame count");
+  const char* fn = "hpe_preprocess_nv12";
+  if (n < 0) return hpe_fail(HPE_EINVAL, "%s: negative frame count", fn);
   const int32_t crop[4] = {crop_x0, crop_y0, crop_w, crop_h};
-  if (int rc = check_nv12("hpe_preprocess_nv12", n, in_h, in_w, y_row_stride, y_frame_stride, uv_row_stride,
-                          uv_frame_stride, matrix, crop, out_h, out_w))
+  if (int rc = check_rect(fn, in_h, in_w, crop, out_h, out_w)) return rc;
+  if (int rc = check_nv12(fn, n, in_h, in_w, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride, matrix))
     return rc;
-  if (int rc = check_count("hpe_preprocess_nv12", "n", n, out_h, out_w)) return rc;
+  if (int rc = check_count(fn, "n", n, out_h, out_w)) return rc;
   if (n == 0) return HPE_OK;
-  if (!y || !uv || !out) return hpe_fail(HPE_EINVAL, "hpe_preprocess_nv12: null argument");
-  const PreNv12Args a = {y, uv,
-                         out,
-                         y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
-                         crop_x0, crop_y0, crop_w, crop_h, out_w, out_h,
-                         (int)(n * out_h * out_w),
-                         matrix,
-                         (float)crop_w / (float)out_w, (float)crop_h / (float)out_h};
-  hipLaunchKernelGGL(preprocess_nv12_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  return launched("hpe_preprocess_nv12");
+  if (!y || !uv || !out) return hpe_fail(HPE_EINVAL, "%s: null argument", fn);
+  const Nv12Src src = {.y = y, .uv = uv, .y_frame = y_frame_stride, .y_row = y_row_stride,
+                       .uv_frame = uv_frame_stride, .uv_row = uv_row_stride, .matrix = matrix};
+  return launch<Nv12Src, false>(fn, src, crop_geom(out, n, out_h, out_w, crop), stream);
 }
 
 extern "C" int hpe_preprocess_rois_nv12(const uint8_t* y, const uint8_t* uv, int64_t n_frames, int32_t in_h,
@@ -608,29 +563,21 @@ extern "C" int hpe_preprocess_rois_nv12(const uint8_t* y, const uint8_t* uv, int
                                         int64_t uv_row_stride, int64_t uv_frame_stride, const int32_t* rois,
                                         int64_t m, int32_t pad_b, int32_t pad_g, int32_t pad_r, int32_t matrix,
                                         float* out, int32_t out_h, int32_t out_w, void* stream) {
-  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: negative frame or ROI count");
-  if (int rc = check_nv12("hpe_preprocess_rois_nv12", n_frames, in_h, in_w, y_row_stride, y_frame_stride,
-                          uv_row_stride, uv_frame_stride, matrix, nullptr, out_h, out_w))
+  const char* fn = "hpe_preprocess_rois_nv12";
+  if (n_frames < 0 || m < 0) return hpe_fail(HPE_EINVAL, "%s: negative frame or ROI count", fn);
+  if (int rc = check_rect(fn, in_h, in_w, nullptr, out_h, out_w)) return rc;
+  if (int rc = check_nv12(fn, n_frames, in_h, in_w, y_row_stride, y_frame_stride, uv_row_stride, uv_frame_stride,
+                          matrix))
     return rc;
-  if (n_frames > 0x7fffffff) return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: batch too large");
-  if (pad_b < 0 || pad_b > 255 || pad_g < 0 || pad_g > 255 || pad_r < 0 || pad_r > 255)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: pad bytes (%d, %d, %d) outside 0..255", pad_b, pad_g,
-                    pad_r);
-  if (int rc = check_count("hpe_preprocess_rois_nv12", "m", m, out_h, out_w)) return rc;
+  if (int rc = check_table(fn, n_frames, pad_b, pad_g, pad_r)) return rc;
+  if (int rc = check_count(fn, "m", m, out_h, out_w)) return rc;
   if (m == 0) return HPE_OK;
   // without frames every row is invalid and nothing is read through `y` or `uv`
-  if (((!y || !uv) && n_frames > 0) || !rois || !out)
-    return hpe_fail(HPE_EINVAL, "hpe_preprocess_rois_nv12: null argument");
-  const RoiNv12Args a = {y, uv,
-                         rois,
-                         out,
-                         y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
-                         (int)n_frames, in_w, in_h, out_w, out_h,
-                         (int)(m * out_h * out_w),
-                         matrix,
-                         pad_b, pad_g, pad_r};
-  hipLaunchKernelGGL(preprocess_rois_nv12_kernel, dim3(pre_grid(a.total)), dim3(PRE_T), 0, (hipStream_t)stream, a);
-  return launched("hpe_preprocess_rois_nv12");
+  if (((!y || !uv) && n_frames > 0) || !rois || !out) return hpe_fail(HPE_EINVAL, "%s: null argument", fn);
+  const Nv12Src src = {.y = y, .uv = uv, .y_frame = y_frame_stride, .y_row = y_row_stride,
+                       .uv_frame = uv_frame_stride, .uv_row = uv_row_stride, .matrix = matrix};
+  return launch<Nv12Src, true>(
+      fn, src, rois_geom(out, m, out_h, out_w, rois, n_frames, in_h, in_w, pad_b, pad_g, pad_r), stream);
 }
 
 // hpe_face_rois: hpe_detect's boxes -> the ROI table of a second pass.  One workgroup per frame: the
@@ -720,5 +667,5 @@ extern "C" int hpe_face_rois(const int32_t* count, const double* boxes, int64_t 
   hipLaunchKernelGGL(face_rois_kernel, dim3((unsigned)n_images), dim3(FROI_T), 0, (hipStream_t)stream, count, boxes,
                      (int)n_images, (int)max_faces, (double)src_x0, (double)src_y0, (double)src_w, (double)src_h,
                      scale, rois, n_rois);
-  return launched("hpe_face_rois");
+  return hpe_launched("hpe_face_rois");
 }

@@ -987,6 +987,12 @@ int hpe_fail(int code, const char* fmt, ...) {
 }
 #define fail hpe_fail
 
+int hpe_launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s launch: %s", fn, hipGetErrorString(e));
+  return HPE_OK;
+}
+
 #define HIPCHK(x)                                                                      \
   do {                                                                                 \
     hipError_t e_ = (x);                                                               \

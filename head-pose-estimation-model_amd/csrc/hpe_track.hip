@@ -223,9 +223,7 @@ extern "C" int hpe_track_reset(int64_t n_streams, int32_t max_tracks, int32_t* s
   const int64_t blocks = (n_streams * max_tracks * TRK_D + 255) / 256;
   hipLaunchKernelGGL(track_reset_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                      (hipStream_t)stream, n_streams, (int)max_tracks, state_i, state_d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_track_reset launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return hpe_launched("hpe_track_reset");
 }
 
 extern "C" int hpe_track(int64_t n_streams, int32_t n_frames, int32_t max_faces, const int32_t* count,
@@ -249,7 +247,5 @@ extern "C" int hpe_track(int64_t n_streams, int32_t n_frames, int32_t max_faces,
   const TrackArgs a = {n_frames, max_faces, max_tracks, count, boxes, keypoints, poses, alpha, 1.0 - alpha,
                        match_iou, max_missed, state_i, state_d, track_out, boxes_out, keypoints_out, poses_out};
   hipLaunchKernelGGL(track_kernel, dim3((unsigned)n_streams), dim3(TRK_T), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_track launch: %s", hipGetErrorString(e));
-  return HPE_OK;
+  return hpe_launched("hpe_track");
 }

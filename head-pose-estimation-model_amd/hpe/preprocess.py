@@ -185,6 +185,19 @@ def _launch(name, device, *args):
         _lib.check(fn(*args, _lib.stream()), name)
 
 
+def _source(x, device, out, what, bgr, rois):
+    """Checked frames of either kind -> (the device frames, the entry point that reads them — the ROI
+    form if ``rois`` —, its arguments before the crop rectangle or the ROI table, those between that and
+    ``out``): the frames' pointers, count, size and strides, and the matrix or the bgr flag where the
+    entry point's signature has it."""
+    x, strides = _device_frames(x, device, out, what)
+    n, h, w = frame_dims(x)
+    if isinstance(x, NV12Frames):
+        lead, colour = (_lib.ptr(x.y), _lib.ptr(x.uv), n, h, w) + strides, (MATRICES[x.matrix],)
+        return (x, 'hpe_preprocess_rois_nv12', lead, colour) if rois else (x, 'hpe_preprocess_nv12', lead + colour, ())
+    return x, 'hpe_preprocess_rois' if rois else 'hpe_preprocess', (_lib.ptr(x), n, h, w, strides), (int(bool(bgr)),)
+
+
 def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
     """frames: uint8 (H, W, 3) or (n, H, W, 3), numpy array or tensor, host or device.  size: int or
     (h, w) of the network input (128: front model, 256: back model).  bgr: the input is BGR (cv2
@@ -192,16 +205,11 @@ def prepare_input(frames, size=128, bgr=True, crop=None, device=None, out=None):
     A device tensor whose pixels are contiguous is read in place through its row stride.  An NV12Frames
     stands for the BGR frames it converts to (hpe_preprocess_nv12); bgr=False is refused with one."""
     oh, ow = _out_hw(size)
-    x, sh = _device_frames(_checked_frames(frames, 'prepare_input', bgr), device, out, 'prepare_input')
+    x, name, lead, colour = _source(_checked_frames(frames, 'prepare_input', bgr), device, out, 'prepare_input', bgr,
+                                    rois=False)
     n, h, w = frame_dims(x)
-    x0, y0, cw, ch = crop_rect(h, w, crop)
     out = _out_tensor(out, n, oh, ow, x.device)
-    if isinstance(x, NV12Frames):
-        _launch('hpe_preprocess_nv12', x.device, _lib.ptr(x.y), _lib.ptr(x.uv), n, h, w, *sh, MATRICES[x.matrix],
-                x0, y0, cw, ch, _lib.ptr(out), oh, ow)
-    else:
-        _launch('hpe_preprocess', x.device, _lib.ptr(x), n, h, w, sh, x0, y0, cw, ch, int(bool(bgr)), _lib.ptr(out),
-                oh, ow)
+    _launch(name, x.device, *lead, *crop_rect(h, w, crop), *colour, _lib.ptr(out), oh, ow)
     return out
 
 
@@ -287,15 +295,9 @@ def prepare_rois(frames, rois, size=128, bgr=True, pad_value=0, device=None, out
     t = roi_table(rois)
     p0, p1, p2 = pad_bytes(pad_value)
     oh, ow = _out_hw(size)
-    x, sh = _device_frames(x, device, out, 'prepare_rois')
+    x, name, lead, colour = _source(x, device, out, 'prepare_rois', bgr, rois=True)
     t = t.to(x.device).contiguous()
-    n, h, w = frame_dims(x)
     m = t.shape[0]
     out = _out_tensor(out, m, oh, ow, x.device)
-    if isinstance(x, NV12Frames):
-        _launch('hpe_preprocess_rois_nv12', x.device, _lib.ptr(x.y), _lib.ptr(x.uv), n, h, w, *sh, _lib.ptr(t), m,
-                p0, p1, p2, MATRICES[x.matrix], _lib.ptr(out), oh, ow)
-    else:
-        _launch('hpe_preprocess_rois', x.device, _lib.ptr(x), n, h, w, sh, _lib.ptr(t), m, p0, p1, p2,
-                int(bool(bgr)), _lib.ptr(out), oh, ow)
+    _launch(name, x.device, *lead, _lib.ptr(t), m, p0, p1, p2, *colour, _lib.ptr(out), oh, ow)
     return out

@@ -383,6 +383,66 @@ def test_gpu_no_rois_and_no_frames():
     assert got.shape == (0, 8, 8, 3) and got.dtype == np.float32
 
 
+# ---- both sources, crop and ROI form: every rectangle of a tiny frame -----------------------------------
+
+TINY = (4, 6)                         # rows x columns: every window is an edge case
+TINY_SIZES = [(5, 3), (1, 1)]
+
+
+def _tiny_inside():
+    """Every rectangle (x0, y0, w, h) inside the tiny frame."""
+    H, W = TINY
+    return [(x0, y0, w, h) for y0 in range(H) for h in range(1, H - y0 + 1) for x0 in range(W)
+            for w in range(1, W - x0 + 1)]
+
+
+def _tiny_outside():
+    """Every rectangle with sides 1..5 and an origin from -4 to one past the far edge that reaches outside."""
+    H, W = TINY
+    return [(x0, y0, w, h) for h in range(1, 6) for w in range(1, 6) for y0 in range(-4, H + 2)
+            for x0 in range(-4, W + 2) if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H]
+
+
+def test_tiny_rectangles_are_what_they_claim():
+    inside, outside = _tiny_inside(), _tiny_outside()
+    assert len(inside) == 210 and len(set(inside)) == 210 and not set(inside) & set(outside)
+    assert len(inside) + len(outside) == 25 * 10 * 12 + sum(1 for r in inside if r[2] > 5)
+    for axis, far in ((0, TINY[1]), (1, TINY[0])):
+        assert {r[axis] for r in outside} == set(range(-4, far + 2))       # odd and even origins, past the far edge
+        assert {r[2 + axis] for r in outside} == set(range(1, 6))
+
+
+@pytest.mark.gpu
+def test_gpu_every_rectangle_of_a_tiny_frame():
+    """The four specializations share their branch structure: each rectangle inside the frame through the
+    crop form and as a row of one ROI table, the rectangles reaching outside as a second table, both
+    sources, all equal to the numpy restatement (and crop == ROI) bit for bit."""
+    import torch
+    import bicubic_ref as B
+    from hpe.preprocess import NV12Frames, prepare_input, prepare_rois
+    y, uv = _nv12((1,), TINY[0], TINY[1], seed=12)
+    bgr = N.nv12_to_bgr(y, uv)
+    sources = {'bgr': torch.from_numpy(bgr).cuda(),
+               'nv12': NV12Frames(torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda())}
+    inside, outside = _tiny_inside(), _tiny_outside()
+    t_in = torch.tensor([(0,) + r for r in inside], dtype=torch.int32).cuda()
+    t_out = np.array([(0,) + r for r in outside], np.int32)
+    for size in TINY_SIZES:
+        want_in = np.stack([B.preprocess(bgr, size, crop=r)[0] for r in inside])
+        want_out = R.prepare_rois(bgr, t_out, size, pad_value=PAD)
+        for name, f in sources.items():
+            crops = torch.cat([prepare_input(f, size=size, crop=r) for r in inside]).cpu().numpy()
+            rois = prepare_rois(f, t_in, size=size, pad_value=PAD).cpu().numpy()
+            for i, r in enumerate(inside):
+                where = '%s %s crop %s' % (name, size, r)
+                np.testing.assert_array_equal(crops[i], want_in[i], err_msg=where)
+                np.testing.assert_array_equal(rois[i], want_in[i], err_msg=where + ' as an ROI')
+            np.testing.assert_array_equal(crops, rois)
+            got = prepare_rois(f, t_out, size=size, pad_value=PAD).cpu().numpy()
+            for i, r in enumerate(outside):
+                np.testing.assert_array_equal(got[i], want_out[i], err_msg='%s %s ROI %s' % (name, size, r))
+
+
 # ---- the conversion itself, through an identity resize -----------------------------------------------
 
 Y16 = [0, 1, 15, 16, 17, 64, 128, 180, 234, 235, 236, 254, 255]
