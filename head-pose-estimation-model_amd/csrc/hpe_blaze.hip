@@ -9,9 +9,9 @@
 //
 // Every op is one fused kernel: the input tile (+ halo) is staged HBM -> LDS once; each wave owns
 // 32 output positions and computes the depthwise result just in time, in registers, as the A
-// operand of v_mfma_f32_32x32x2_f32 (lane = position, k = channel, 4 channels per ds_read_b128 per
-// tap; fp16-split MFMA, see mfma_split), so the depthwise output never exists in memory; the
-// pointwise weights (W^T, as fp16 hi/lo pairs) sit in LDS and
+// operand of the fp16-split MFMA (three v_mfma_f32_32x32x8_f16 per 8 channels, see mfma_split;
+// lane = position, k = channel, 4 channels per ds_read_b128 per tap), so the depthwise output never
+// exists in memory; the pointwise weights (W^T, as fp16 hi/lo pairs) sit in LDS and
 // the epilogue adds bias + residual (read back from the staged tile) + ReLU and writes NHWC.
 // fp32 arithmetic throughout (every GEMM as fp16 MFMA products at fp32 accuracy): per-op HBM traffic =
 // input + output, the depthwise layers' 1.9 FLOP/B make the chain HBM-bound.
@@ -61,6 +61,75 @@ __device__ __forceinline__ f32x16 mfma_split(f32x4 av, f32x4 wpk, f32x16 acc) {
   return __builtin_amdgcn_mfma_f32_32x32x8f16(ah, bh, acc, 0, 0, 0);
 }
 
+// ---- the arithmetic the kernels below share, one copy each: what keeps the per-op, stage and
+// front plans bit-identical (the sites that could not use a piece say so) ----
+
+// depthwise 3x3 on one channel quad: the bias quad, then one tap (one fmaf per channel) at a time in
+// tap order (ky, kx).  x(tp) / w(tp) give tap tp's input and weight quads, each caller its own way:
+// LDS tile, ring rows, DPP shifts.  bf_direct_kernel and bff_block run the same loop over dw_tap in
+// place: through dw_quad their registers changed (direct<S, 1, 2>: 130 -> 142 VGPRs, 3 -> 2 waves per
+// SIMD; the front: 228 -> 231)
+__device__ __forceinline__ f32x4 dw_tap(f32x4 av, f32x4 xv, f32x4 wv) {
+  av.x = fmaf(xv.x, wv.x, av.x);
+  av.y = fmaf(xv.y, wv.y, av.y);
+  av.z = fmaf(xv.z, wv.z, av.z);
+  av.w = fmaf(xv.w, wv.w, av.w);
+  return av;
+}
+template <class X, class Wt>
+__device__ __forceinline__ f32x4 dw_quad(f32x4 bias, X x, Wt w) {
+  f32x4 av = bias;
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp) av = dw_tap(av, x(tp), w(tp));
+  return av;
+}
+
+// accumulator register g of lane half `half` <-> position (row) of the 32x32 MFMA tile
+__device__ __forceinline__ int acc_pos(int g, int half) { return (g & 3) + 8 * (g >> 2) + 4 * half; }
+
+// MaxPool 2x2 residual: t = the window's top-left element, c / r = column / row strides in floats
+__device__ __forceinline__ float max_pool2(const float* t, int c, int r) {
+  return fmaxf(fmaxf(t[0], t[c]), fmaxf(t[r], t[r + c]));
+}
+
+// output channel n of position pos: split > 0 sends channels [0, split) to dst and [split, cout) to
+// dst2 (the fused detector heads), otherwise dst has channel stride ostride
+__device__ __forceinline__ void store_out(float* dst, float* dst2, int64_t pos, int n, float v, int split, int cout,
+                                          int ostride) {
+  if (split) {
+    if (n < split) dst[pos * split + n] = v;
+    else if (n < cout) dst2[pos * (cout - split) + (n - split)] = v;
+  } else if (n < ostride) {
+    dst[pos * ostride + n] = v;
+  }
+}
+
+// W^T [nct * 32][cinp] at P_ + pww (rows >= coutp zero) -> LDS rows of stride ks as split_w pairs.
+// Batches of 8 float4 per thread: every load of a batch is issued (from a clamped, always valid
+// address) before the first LDS write, so a workgroup's staging costs ~one HBM round trip per
+// batch instead of one per element (a conditional load per element serialises on vmcnt(0))
+__device__ __forceinline__ void stage_wt(float* wt, const float* P_, int pww, int nct, int coutp, int cinp, int ks) {
+  const int kq = cinp >> 2, nthr = blockDim.x;
+  const int nW = nct * 32 * kq;
+  for (int e0 = threadIdx.x; e0 < nW; e0 += 8 * nthr) {
+    f32x4 v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = e0 + i * nthr;
+      const int n = e / kq, q = e - n * kq;
+      const bool ok = e < nW && n < coutp;
+      v[i] = ld4(P_ + pww + (ok ? n * cinp + 4 * q : 0));
+      if (!ok) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = e0 + i * nthr;
+      const int n = e / kq, q = e - n * kq;
+      if (e < nW) *(f32x4*)(wt + n * ks + 4 * q) = split_w(v[i]);
+    }
+  }
+}
+
 // XCD-aware work id: consecutive work ids (the tiles of one image, whose halos overlap) stay on
 // one XCD's L2 (hardware dispatches workgroups round-robin over the 8 XCDs).
 __device__ __forceinline__ int xcd_work_id(int nwg) {
@@ -81,6 +150,48 @@ __device__ __forceinline__ int xcd_work_id(int nwg) {
 // ------------------------------------------------------------------------------------------------
 #define STEM_KS 45
 #define STEM_NK 6   // K-steps of 8 k per lane half
+// weights: W^T padded [32][90] at P_ + pww (k = (ky*5 + kx)*3 + c, ky < 6), lane n = l32, its half's
+// 45 k as split fragments of K-step s = k-local 8 s .. 8 s + 7, scaled by s1 (max |w| of the channel
+// in [2^13, 2^14)); z = acc * inv + bias, inv = 1 / (C s1)
+__device__ __forceinline__ void stem_weights(const float* P_, int pww, int l32, int half, SplitW (&wsp)[STEM_NK],
+                                             float& inv) {
+  f32x8 v[STEM_NK];
+  float mx = 0.f;
+#pragma unroll
+  for (int s = 0; s < STEM_NK; ++s) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int q = 8 * s + j;
+      v[s][j] = q < STEM_KS ? P_[pww + l32 * 90 + half * STEM_KS + q] : 0.f;
+      mx = fmaxf(mx, fabsf(v[s][j]));
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  const float s1 = pow2_scale(mx, 13);
+  inv = SPLIT_INV_C / s1;
+#pragma unroll
+  for (int s = 0; s < STEM_NK; ++s) wsp[s] = split_w8(v[s] * s1);
+}
+// the K loop of one 32-position chunk: t0..t2 = the lane's window rows ky - 3 half = 0..2 at its
+// first column, element (kx, c) at 3 kx + c; k-local q is (ky - 3 half, kx, c) = (q / 15, q / 3 % 5,
+// q % 3), all compile-time
+__device__ __forceinline__ f32x16 stem_k(const float* t0, const float* t1, const float* t2,
+                                         const SplitW (&wsp)[STEM_NK]) {
+  const float* tr[3] = {t0, t1, t2};
+  f32x16 acc = {};
+#pragma unroll
+  for (int s = 0; s < STEM_NK; ++s) {
+    f32x8 xv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int q = 8 * s + j;
+      xv[j] = q < STEM_KS ? tr[q / 15][((q / 3) % 5) * 3 + q % 3] : 0.f;
+    }
+    acc = mfma3_dw(split_d8(xv), wsp[s], acc);
+  }
+  return acc;
+}
+
 __global__ void __launch_bounds__(256) bf_stem_kernel(BfArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int* f = a.f;
@@ -94,29 +205,9 @@ __global__ void __launch_bounds__(256) bf_stem_kernel(BfArgs a) {
   const int64_t img = wid / tpi;
   const int oy0 = (wid - (int)img * tpi) * TH;
   const float* P_ = a.params;
-  // weights: W^T padded [32][90] (k = (ky*5 + kx)*3 + c, ky < 6), lane n = l32, its half's 45 k as
-  // split fragments of K-step s = k-local 8 s .. 8 s + 7, scaled by s1 (max |w| of the channel in
-  // [2^13, 2^14)); z = acc * inv + bias, inv = 1 / (C s1)
   SplitW wsp[STEM_NK];
   float inv;
-  {
-    f32x8 v[STEM_NK];
-    float mx = 0.f;
-#pragma unroll
-    for (int s = 0; s < STEM_NK; ++s) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = 8 * s + j;
-        v[s][j] = q < STEM_KS ? P_[f[BFO_PWW] + l32 * 90 + half * STEM_KS + q] : 0.f;
-        mx = fmaxf(mx, fabsf(v[s][j]));
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float s1 = pow2_scale(mx, 13);
-    inv = SPLIT_INV_C / s1;
-#pragma unroll
-    for (int s = 0; s < STEM_NK; ++s) wsp[s] = split_w8(v[s] * s1);
-  }
+  stem_weights(P_, f[BFO_PWW], l32, half, wsp, inv);
   // image tile: LDS row r <-> image row 2*oy0 - padt + r; a row is W*3 contiguous floats placed at
   // column padl (zeros around), no per-element division
   const int iy0 = oy0 * 2 - f[BFO_PADT];
@@ -148,22 +239,12 @@ __global__ void __launch_bounds__(256) bf_stem_kernel(BfArgs a) {
     const int p = chunk * 32 + l32;
     const int oyl = p >> lgWo, ox = p & (Wo - 1);
     const float* t = lds + (oyl * 2 + half * 3) * rowf + ox * 6;
-    f32x16 acc = {};
-#pragma unroll
-    for (int s = 0; s < STEM_NK; ++s) {
-      f32x8 xv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int q = 8 * s + j;   // compile-time: (ky - 3 half, kx, c) = (q / 15, q / 3 % 5, q % 3)
-        xv[j] = q < STEM_KS ? t[(q / 15) * rowf + ((q / 3) % 5) * 3 + q % 3] : 0.f;
-      }
-      acc = mfma3_dw(split_d8(xv), wsp[s], acc);
-    }
+    const f32x16 acc = stem_k(t, t + rowf, t + 2 * rowf, wsp);
     if (l32 < Cout) {
       float* drow = a.dst + ((img * Ho + oy0) * Wo) * Cout + l32;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int q = chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;   // q = qy * Wo + qx
+        const int q = chunk * 32 + acc_pos(g, half);   // q = qy * Wo + qx
         const float v = fmaf(acc[g], inv, bias);
         drow[q * Cout] = v > 0.f ? v : 0.f;
       }
@@ -200,31 +281,12 @@ __global__ void __launch_bounds__(512) bf_block_kernel(BfArgs a) {
   const int64_t img0 = NI > 1 ? (int64_t)wid * NI : wid / tpi;
   const int oy0 = NI > 1 ? 0 : (wid - (int)img0 * tpi) * TH;
 
-  // ---- stage W^T (rows >= Coutp zero), depthwise table, input tile (zero outside the image) ----
-  // batches of 8 float4 per thread: every load of a batch is issued (from a clamped, always valid
-  // address) before the first LDS write, so a workgroup's staging costs ~one HBM round trip per
-  // batch instead of one per element (a conditional load per element serialises on vmcnt(0))
+  // ---- stage W^T (rows >= Coutp zero), depthwise table, input tile (zero outside the image; the
+  // same batches of 8 clamped loads as stage_wt) ----
   const int kq = Cinp >> 2;
   const int nthr = blockDim.x;
   {
-    const int nW = NCT * 32 * kq;
-    for (int e0 = threadIdx.x; e0 < nW; e0 += 8 * nthr) {
-      f32x4 v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int e = e0 + i * nthr;
-        const int n = e / kq, q = e - n * kq;
-        const bool ok = e < nW && n < Coutp;
-        v[i] = ld4(P_ + f[BFO_PWW] + (ok ? n * Cinp + 4 * q : 0));
-        if (!ok) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int e = e0 + i * nthr;
-        const int n = e / kq, q = e - n * kq;
-        if (e < nW) *(f32x4*)(wt + n * KS + 4 * q) = split_w(v[i]);
-      }
-    }
+    stage_wt(wt, P_, f[BFO_PWW], NCT, Coutp, Cinp, KS);
     const int iy0 = oy0 * S - padt;
     const int nT = NI * ROWS * COLS * kq;
     for (int e0 = threadIdx.x; e0 < nT; e0 += 8 * nthr) {
@@ -272,16 +334,9 @@ __global__ void __launch_bounds__(512) bf_block_kernel(BfArgs a) {
     for (int c0 = 4 * half; c0 < Cinp; c0 += 8) {
       f32x4 av;
       if (DW) {
-        av = ld4(dwt + 9 * Cinp + c0);
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const f32x4 xv = ld4(tb + (tp / 3) * colsCS + (tp % 3) * CS + c0);
-          const f32x4 wv = ld4(dwt + tp * Cinp + c0);
-          av.x = fmaf(xv.x, wv.x, av.x);
-          av.y = fmaf(xv.y, wv.y, av.y);
-          av.z = fmaf(xv.z, wv.z, av.z);
-          av.w = fmaf(xv.w, wv.w, av.w);
-        }
+        av = dw_quad(
+            ld4(dwt + 9 * Cinp + c0), [&](int tp) { return ld4(tb + (tp / 3) * colsCS + (tp % 3) * CS + c0); },
+            [&](int tp) { return ld4(dwt + tp * Cinp + c0); });
       } else {
         av = ld4(tb + c0);
       }
@@ -298,28 +353,19 @@ __global__ void __launch_bounds__(512) bf_block_kernel(BfArgs a) {
       const float bias = P_[f[BFO_PWB] + n];
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int q = chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
+        const int q = chunk * 32 + acc_pos(g, half);
         const int ql = q >> lgP, qr = q & ((1 << lgP) - 1);
         const int qy = qr >> lgWo, qx = qr & (Wo - 1);
         float v = acc[nc][g] + bias;
         if (res == BF_RES_ID) {
           if (n < Cinp) v += tile[(ql * ROWS + qy + padt) * colsCS + (qx + padl) * CS + n];
         } else if (res == BF_RES_MAXPOOL) {
-          if (n < Cinp) {
-            const float* t = tile + (ql * ROWS + 2 * qy) * colsCS + 2 * qx * CS + n;
-            v += fmaxf(fmaxf(t[0], t[CS]), fmaxf(t[colsCS], t[colsCS + CS]));
-          }
+          if (n < Cinp) v += max_pool2(tile + (ql * ROWS + 2 * qy) * colsCS + 2 * qx * CS + n, CS, colsCS);
         }
         if (relu) v = v > 0.f ? v : 0.f;
         const int64_t img = img0 + ql;
         if (img >= a.nimg) continue;
-        const int64_t pos = (img * Ho + oy0 + qy) * Wo + qx;
-        if (split) {
-          if (n < split) a.dst[pos * split + n] = v;
-          else if (n < Cout) a.dst2[pos * (Cout - split) + (n - split)] = v;
-        } else if (n < ostride) {
-          a.dst[pos * ostride + n] = v;
-        }
+        store_out(a.dst, a.dst2, (img * Ho + oy0 + qy) * Wo + qx, n, v, split, Cout, ostride);
       }
     }
   }
@@ -435,23 +481,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) b
       for (int nc = 0; nc < NC; ++nc) acc[nc] = (f32x16){};
 #pragma unroll 1
       for (int c0 = 4 * half; c0 < (CINP ? CINP : Cinp); c0 += 8) {
-        f32x4 av = ld4(dwt + 9 * Cinp + c0);
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const float* rp = tp < 3 ? r0 : (tp < 6 ? r1 : r2);
-          const f32x4 xv = ld4(rp + (tp % 3) * CS + c0);
-          const f32x4 wv = ld4(dwt + tp * Cinp + c0);
-          av.x = fmaf(xv.x, wv.x, av.x);
-          av.y = fmaf(xv.y, wv.y, av.y);
-          av.z = fmaf(xv.z, wv.z, av.z);
-          av.w = fmaf(xv.w, wv.w, av.w);
-        }
+        const f32x4 av = dw_quad(
+            ld4(dwt + 9 * Cinp + c0),
+            [&](int tp) { return ld4((tp < 3 ? r0 : (tp < 6 ? r1 : r2)) + (tp % 3) * CS + c0); },
+            [&](int tp) { return ld4(dwt + tp * Cinp + c0); });
 #pragma unroll
         for (int nc = 0; nc < NC; ++nc) {
           acc[nc] = mfma_split(av, ld4(wb + nc * 32 * KS + c0), acc[nc]);
         }
       }
-      // epilogue: register g <-> step position q = p0 + 4*half + (g&3) + 8*(g>>2): output row
+      // epilogue: register g <-> step position q = p0 + acc_pos(g, half): output row
       // oy0 + (q >> lgWo) (oyA, or oyA + 1 when the chunk wraps), column q & (Wo - 1); the output
       // address is linear in q.  Residual rows of oyA / oyA + 1 in the ring:
       const float *rA, *rA1 = nullptr, *rB, *rB1 = nullptr;
@@ -473,7 +512,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) b
         const bool has_res = n < Cinp;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const int d = (g & 3) + 8 * (g >> 2);
+          const int d = acc_pos(g, 0);  // the lane half's 4 positions are in `out`
           float v = acc[nc][g] + bias;
           if (has_res) {
             const int q = p0 + 4 * half + d;
@@ -482,6 +521,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) b
             if (S == 1) {
               v += (second ? rB : rA)[xg * CS + n];
             } else {
+              // max_pool2 on two ring slots: no constant row stride (as their distance it cost the
+              // specialised s2 kernels registers: <2, 0, 48, 48> 24 -> 46 spilled VGPRs)
               const float* t0 = (second ? rB : rA) + 2 * xg * CS + n;
               const float* t1 = (second ? rB1 : rA1) + 2 * xg * CS + n;
               v += fmaxf(fmaxf(t0[0], t0[CS]), fmaxf(t1[0], t1[CS]));
@@ -542,9 +583,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) b
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
 // direct: the fused block for the small maps (16x16, 8x8) and the detector heads.  Persistent
 // workgroups keep W^T (fp16 hi/lo pairs) and the depthwise table in LDS for the whole launch; each
 // wave task is a 32-position chunk of one image with ALL output-channel chunks (no depthwise
@@ -568,28 +606,9 @@ __global__ void __launch_bounds__(256) bf_direct_kernel(BfArgs a) {
   float* dwt = wt + NCT * 32 * KS;
   const int kq = Cinp >> 2;
   const int nthr = blockDim.x;
-  {  // W^T (split) + depthwise table, batched loads
-    const int nW = NCT * 32 * kq;
-    for (int e0 = threadIdx.x; e0 < nW; e0 += 8 * nthr) {
-      f32x4 v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int e = e0 + i * nthr;
-        const int n = e / kq, q = e - n * kq;
-        const bool ok = e < nW && n < Coutp;
-        v[i] = ld4(P_ + f[BFO_PWW] + (ok ? n * Cinp + 4 * q : 0));
-        if (!ok) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int e = e0 + i * nthr;
-        const int n = e / kq, q = e - n * kq;
-        if (e < nW) *(f32x4*)(wt + n * KS + 4 * q) = split_w(v[i]);
-      }
-    }
-    if (DW)
-      for (int i = threadIdx.x; i < 10 * kq; i += nthr) *(f32x4*)(dwt + 4 * i) = ld4(P_ + f[BFO_DWW] + 4 * i);
-  }
+  stage_wt(wt, P_, f[BFO_PWW], NCT, Coutp, Cinp, KS);
+  if (DW)
+    for (int i = threadIdx.x; i < 10 * kq; i += nthr) *(f32x4*)(dwt + 4 * i) = ld4(P_ + f[BFO_DWW] + 4 * i);
   __syncthreads();
 
   const int cpi = (Ho * Wo) >> 5;
@@ -624,14 +643,8 @@ __global__ void __launch_bounds__(256) bf_direct_kernel(BfArgs a) {
         for (int tp = 0; tp < 9; ++tp) xv[tp] = ld4(xi + toff[tp] + c0);
         av = ld4(dwt + 9 * Cinp + c0);
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) {
-          const f32x4 x = (tmask >> tp) & 1u ? xv[tp] : f32x4{0.f, 0.f, 0.f, 0.f};
-          const f32x4 wv = ld4(dwt + tp * Cinp + c0);
-          av.x = fmaf(x.x, wv.x, av.x);
-          av.y = fmaf(x.y, wv.y, av.y);
-          av.z = fmaf(x.z, wv.z, av.z);
-          av.w = fmaf(x.w, wv.w, av.w);
-        }
+        for (int tp = 0; tp < 9; ++tp)  // dw_quad's loop (see there)
+          av = dw_tap(av, (tmask >> tp) & 1u ? xv[tp] : f32x4{0.f, 0.f, 0.f, 0.f}, ld4(dwt + tp * Cinp + c0));
       } else {
         av = ld4(xi + toff[4] + c0);
       }
@@ -646,25 +659,16 @@ __global__ void __launch_bounds__(256) bf_direct_kernel(BfArgs a) {
       const float bias = P_[f[BFO_PWB] + n];
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int q = chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
+        const int q = chunk * 32 + acc_pos(g, half);
         const int qy = q >> lgWo, qx = q & (Wo - 1);
         float v = acc[nc][g] + bias;
         if (res == BF_RES_ID) {
           if (n < Cinp) v += xi[(qy * W + qx) * Cinp + n];
         } else if (res == BF_RES_MAXPOOL) {
-          if (n < Cinp) {
-            const float* t = xi + ((2 * qy) * W + 2 * qx) * Cinp + n;
-            v += fmaxf(fmaxf(t[0], t[Cinp]), fmaxf(t[W * Cinp], t[W * Cinp + Cinp]));
-          }
+          if (n < Cinp) v += max_pool2(xi + ((2 * qy) * W + 2 * qx) * Cinp + n, Cinp, W * Cinp);
         }
         if (relu) v = v > 0.f ? v : 0.f;
-        const int64_t pos = (img * Ho + qy) * Wo + qx;
-        if (split) {
-          if (n < split) a.dst[pos * split + n] = v;
-          else if (n < Cout) a.dst2[pos * (Cout - split) + (n - split)] = v;
-        } else if (n < ostride) {
-          a.dst[pos * ostride + n] = v;
-        }
+        store_out(a.dst, a.dst2, (img * Ho + qy) * Wo + qx, n, v, split, Cout, ostride);
       }
     }
   }
@@ -701,9 +705,9 @@ struct BfStageArgs {
 //   LDS: map [HW][CS] (in place: a block's outputs stay in registers until every wave has read
 //        its inputs, one barrier, then overwrite them; a stride-2 block's smaller output overlays
 //        the start of its input the same way) | W^T of the current op (fp16 hi/lo pairs) | dw table
-//   per op: <= 8 wave tasks (32-position chunk x group of NC output-channel chunks of 32), the same
-//        arithmetic as bf_block_kernel / bf_direct_kernel (depthwise bias + 9 taps in order, fp16-
-//        split MFMA over ascending channel quads, bias, residual, ReLU), so the outputs are
+//   per op: <= 8 wave tasks (32-position chunk x group of NC output-channel chunks of 32), the
+//        per-op kernels' arithmetic through the same functions (dw_quad, mfma_split over ascending
+//        channel quads, then bias, residual (max_pool2), ReLU), so the outputs are
 //        bit-identical to the per-op path; the next op's weights are loaded into registers while
 //        this op computes and written to LDS after its barrier (two barriers per op).
 //   round 6: NC is a template parameter of the task (a runtime NC made every MFMA triple
@@ -764,39 +768,10 @@ __device__ __forceinline__ float dpp_from_next(float v) {  // lane i <- lane i +
 }
 
 #define BFS_MAXNC 3  // output-channel chunks per wave task (acc registers: 16 each)
-#ifndef BFS_PIPE
-#define BFS_PIPE 0   // 1: the K loop prefetches the next step's taps / W^T (more VGPRs: spills)
-#endif
-#ifndef BFS_PIPE1
-#define BFS_PIPE1 0  // 1: the same for the single-chunk (NC = 1) tasks only (8x8 ops, heads): neutral
-#endif
-#ifdef BFS_SB_ON   // a scheduling barrier after each step's reads (measured slower: more spills)
-#define BFS_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define BFS_SB() do {} while (0)
-#endif
 // the streamed maps (the stage's source rows and the taps, each touched once) bypass L2 retention
 // (non-temporal), so the stage's weights, re-read by every frame, stay L2-resident
-#ifndef BFS_NT
-#define BFS_NT 1
-#endif
-__device__ __forceinline__ f32x4 ld4_nt(const float* p) {
-  if (BFS_NT) return __builtin_nontemporal_load((const f32x4*)p);
-  return *(const f32x4*)p;
-}
-__device__ __forceinline__ void st4_nt(float* p, f32x4 v) {
-  if (BFS_NT) __builtin_nontemporal_store(v, (f32x4*)p);
-  else *(f32x4*)p = v;
-}
-
-
-// the prefetched reads of one K-step (8 input channels; this lane's quad c0 = 4 half + 8 k); the
-// depthwise table rows (10 broadcast quads) are read inside the step, ahead of the taps' DPP work
-template <int NT, int NC>
-struct BfsK {
-  f32x4 x[NT];                  // source taps (DPP: the 3 centre-column reads)
-  f32x4 w[NC];                  // W^T quads (fp16 hi/lo pairs) of the NC output-channel chunks
-};
+__device__ __forceinline__ f32x4 ld4_nt(const float* p) { return __builtin_nontemporal_load((const f32x4*)p); }
+__device__ __forceinline__ void st4_nt(float* p, f32x4 v) { __builtin_nontemporal_store(v, (f32x4*)p); }
 
 // one wave task of op o: acc[j] (j < NC) = the final outputs (bias, residual, ReLU applied) of
 // output-channel chunk grp * NC + j at the 32 positions of chunk `chunk`.  src: the source map
@@ -856,28 +831,29 @@ __device__ __forceinline__ void bfs_task(const BfSub& o, const float* src, int s
 #pragma unroll
   for (int j = 0; j < NC; ++j) acc[j] = (f32x16){};
 
-  using K = BfsK<NT, NC>;
-  typedef f32x4 Dv[ND > 0 ? ND : 1];
-  auto load = [&](int c0, K& r) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) r.x[t] = ld4(src + toff[DPP ? 3 * t + 1 : t] + c0);
-#pragma unroll
-    for (int j = 0; j < NC; ++j) r.w[j] = ld4(wt + wrow[j] + c0);
-  };
-  // the step's depthwise table rows, issued as one batch ahead of the prefetch of the next step
-  // (left to the scheduler, each row was read behind its own lgkmcnt(0): an LDS round trip per row)
-  auto load_dw = [&](int c0, Dv& dv) {
+  // K loop, one step per 8 input channels (this lane's quad c0 = 4 half + 8 k), one buffer (a
+  // software-pipelined loop spilled and ran slower).  The step's depthwise table rows
+  // (10 broadcast quads) are issued as one batch ahead of the taps (left to the scheduler, each row
+  // was read behind its own lgkmcnt(0): an LDS round trip per row)
+  const int nks = cinp >> 3;
+  int c0 = 4 * half;
+  for (int k = 0; k < nks; ++k, c0 += 8) {
+    f32x4 dv[ND > 0 ? ND : 1];
+    f32x4 x[NT];  // source taps (DPP: the 3 centre-column reads)
+    f32x4 w[NC];  // W^T quads (fp16 hi/lo pairs) of the NC output-channel chunks
 #pragma unroll
     for (int t = 0; t < ND; ++t) dv[t] = ld4(dwt + t * cinp + c0);
-  };
-  auto step = [&](const K& r, const Dv& dv) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) x[t] = ld4(src + toff[DPP ? 3 * t + 1 : t] + c0);
+#pragma unroll
+    for (int j = 0; j < NC; ++j) w[j] = ld4(wt + wrow[j] + c0);
     f32x4 av;
     if constexpr (DW) {
       f32x4 xv[9];
       if constexpr (DPP) {
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-          const f32x4 c = r.x[dy];
+          const f32x4 c = x[dy];
           xv[3 * dy + 1] = c;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -887,57 +863,17 @@ __device__ __forceinline__ void bfs_task(const BfSub& o, const float* src, int s
         }
       } else {
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) xv[tp] = r.x[tp];
+        for (int tp = 0; tp < 9; ++tp) xv[tp] = x[tp];
       }
-      av = dv[9];
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) {
-        const f32x4 x = !masked(tp) || ((tmask >> tp) & 1u) ? xv[tp] : f32x4{0.f, 0.f, 0.f, 0.f};
-        const f32x4 wv = dv[tp];
-        av.x = fmaf(x.x, wv.x, av.x);
-        av.y = fmaf(x.y, wv.y, av.y);
-        av.z = fmaf(x.z, wv.z, av.z);
-        av.w = fmaf(x.w, wv.w, av.w);
-      }
+      av = dw_quad(
+          dv[9],
+          [&](int tp) { return !masked(tp) || ((tmask >> tp) & 1u) ? xv[tp] : f32x4{0.f, 0.f, 0.f, 0.f}; },
+          [&](int tp) { return dv[tp]; });
     } else {
-      av = r.x[0];
+      av = x[0];
     }
 #pragma unroll
-    for (int j = 0; j < NC; ++j) acc[j] = mfma_split(av, r.w[j], acc[j]);
-  };
-  // K loop, two steps per trip: the next step's reads are issued before this step's arithmetic
-  // (BFV_BAND: one buffer, its registers hold the second band's staged rows meanwhile; BFV_GLOBAL
-  // too, the generic fallback)
-  const int nks = cinp >> 3;
-  int c0 = 4 * half;
-  Dv dv;
-  if constexpr (V == BFV_BAND || V == BFV_GLOBAL || !(BFS_PIPE || (BFS_PIPE1 && NC == 1))) {
-    for (int k = 0; k < nks; ++k, c0 += 8) {
-      K A;
-      load_dw(c0, dv);
-      load(c0, A);
-      if constexpr (V != BFV_BAND && V != BFV_GLOBAL) BFS_SB();
-      step(A, dv);
-    }
-  } else {
-    K A, B;
-    load(c0, A);
-    int k = 0;
-    for (; k + 2 <= nks; k += 2, c0 += 16) {
-      load_dw(c0, dv);
-      load(c0 + 8, B);
-      BFS_SB();
-      step(A, dv);
-      load_dw(c0 + 8, dv);
-      load(k + 2 < nks ? c0 + 16 : c0 + 8, A);
-      BFS_SB();
-      step(B, dv);
-    }
-    if (nks & 1) {
-      load_dw(c0, dv);
-      BFS_SB();
-      step(A, dv);
-    }
+    for (int j = 0; j < NC; ++j) acc[j] = mfma_split(av, w[j], acc[j]);
   }
 
   // epilogue values: lane = output channel n, registers = 16 positions of the chunk
@@ -946,16 +882,13 @@ __device__ __forceinline__ void bfs_task(const BfSub& o, const float* src, int s
     const int n = n0 + 32 * j;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int q = chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
+      const int q = chunk * 32 + acc_pos(g, half);
       const int qy = q >> lgWo, qx = q & (wo - 1);
       float v = acc[j][g] + bias[j];
       if (RES == BF_RES_ID) {
         if (n < cinp) v += src[((qy - iyb) * ow + qx) * ss + n];
       } else if (RES == BF_RES_MAXPOOL) {
-        if (n < cinp) {
-          const float* t = src + ((2 * qy - iyb) * ow + 2 * qx) * ss + n;
-          v += fmaxf(fmaxf(t[0], t[ss]), fmaxf(t[ow * ss], t[ow * ss + ss]));
-        }
+        if (n < cinp) v += max_pool2(src + ((2 * qy - iyb) * ow + 2 * qx) * ss + n, ss, ow * ss);
       }
       if (DW) v = v > 0.f ? v : 0.f;
       acc[j][g] = v;
@@ -1026,23 +959,14 @@ __device__ __forceinline__ void bfs_store(const BfSub& o, const float* const* bu
     if (n >= coutp) continue;
     if (!head) {
 #pragma unroll
-      for (int g = 0; g < 16; ++g) map[(chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half) * cs + n] = acc[j][g];
+      for (int g = 0; g < 16; ++g) map[(chunk * 32 + acc_pos(g, half)) * cs + n] = acc[j][g];
       continue;
     }
+    // plain stores: 4-B non-temporal stores of these scattered head outputs reach HBM as partial
+    // lines (the stage's PMC write bytes 216 MB with them, 190 MB without)
 #pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int q = chunk * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
-      const float v = acc[j][g];
-      const int64_t pos = img * hwo + q;
-      // plain stores: 4-B non-temporal stores of these scattered head outputs reach HBM as partial
-      // lines (the stage's PMC write bytes 216 MB with them, 190 MB without)
-      if (split) {
-        if (n < split) gd[pos * split + n] = v;
-        else if (n < cout) gd2[pos * (cout - split) + (n - split)] = v;
-      } else if (n < ostride) {
-        gd[pos * ostride + n] = v;
-      }
-    }
+    for (int g = 0; g < 16; ++g)
+      store_out(gd, gd2, img * hwo + (chunk * 32 + acc_pos(g, half)), n, acc[j][g], split, cout, ostride);
   }
 }
 
@@ -1219,10 +1143,10 @@ static bf_fn pick_direct(int s, int dw, int nc) {
 // land in the next layer's input ring (4 rows: the 3 its 3x3 window reads + the one being
 // written) — and only the frame (196 KB) and the last block's 32x32x48 output (196 KB) touch HBM.
 //   * wave roles (fixed; waves w and w + 4 share a SIMD): w0/w1 the stem's two 32-position chunks of
-//     a 64-wide row, w2/w3 block 1, w4/w5 block 2, w6 block 3 (odd phases, s2 32-wide) and the
-//     frame's input rows (LDS-DMA two phases ahead into a 10-row ring: a phase waits only for the
-//     pieces issued in the phase before it, not for its own), w7 block 4 (even) and block 5 (odd,
-//     its rows to HBM).  The
+//     a 64-wide row, w2 both chunks of block 1, w4/w5 block 2, w6 block 3 (odd phases, s2 32-wide)
+//     and the frame's input rows (LDS-DMA two phases ahead into a 10-row ring: a phase waits only
+//     for the pieces issued in the phase before it, not for its own), w7 and w3 one output-channel
+//     chunk each of block 4 (even phases) and block 5 (odd, its rows to HBM).  The
 //     pointwise weights of a wave's layers live in its registers (fp16 hi/lo pairs), the depthwise
 //     tables in LDS.
 //   * phase p (one workgroup barrier each, 76 per frame): stem row p, block-1 row p - 2, block-2
@@ -1230,15 +1154,12 @@ static bf_fn pick_direct(int s, int dw, int nc) {
 //     every row a layer reads was written in an earlier phase, and the ring slot a layer writes
 //     (row mod 4) is one no layer reads in that phase.  The bottom padding row of each map is
 //     written as zeros by its producer, the top one and the column halos are the per-frame zeroing.
-//   * the same arithmetic as bf_stem_kernel / bf_rows_kernel (stem: fp16-split MFMA over the same K
-//     order and scales; blocks: depthwise bias + 9 taps in order, mfma_split per 8 channels in the
-//     same order, bias + residual + ReLU): the output is bit-identical to the per-op launches.
+//   * the per-op kernels' arithmetic through the same functions (stem: stem_weights + stem_k;
+//     blocks: dw_quad's loop over dw_tap, mfma_split per 8 channels in ascending order, then bias +
+//     residual (max_pool2) + ReLU): the output is bit-identical to the per-op launches.
 // The geometry is the BlazeFace backbone's (host-checked against the plan records).
 // ------------------------------------------------------------------------------------------------
 #define BFF_NW 8
-#ifndef BFF_SPLIT45
-#define BFF_SPLIT45 1   // w2 both block-1 chunks; w3 and w7 one output-channel chunk each of blocks 4 / 5
-#endif
 #ifdef BFF_STAMPS   // per-wave busy cycles (task time, barrier waits excluded) of workgroup 0
 #define BFF_BAR() do { bff_busy += __builtin_amdgcn_s_memtime() - bff_t0; bar_lds(); bff_t0 = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -1289,9 +1210,7 @@ __device__ __forceinline__ void bff_wload(const BfFrontArgs& a, f32x4 (&wr)[NCN]
   }
 }
 
-// one 32-position chunk (c) of output row oy of block K: bf_rows_kernel's compute + epilogue; the
-// output goes to block K + 1's ring (row slot oy & 3) or, for K = 5, to HBM; zero: the bottom
-// padding row (zeros)
+// the depthwise table (9 taps + bias) of block K for this lane's channel quads
 template <int K>
 __device__ __forceinline__ void bff_dwload(const BfFrontArgs& a, f32x4 (&dwr)[BffL<K>::CINP / 8][10], int half) {
 #pragma unroll
@@ -1300,6 +1219,9 @@ __device__ __forceinline__ void bff_dwload(const BfFrontArgs& a, f32x4 (&dwr)[Bf
     for (int t = 0; t < 10; ++t) dwr[k][t] = ld4(a.params + a.dww[K] + t * BffL<K>::CINP + 4 * half + 8 * k);
 }
 
+// one 32-position chunk (c) of output row oy of block K, the arithmetic of bf_rows_kernel's tasks
+// (dw_tap in tap order, mfma_split, bias + residual + ReLU); the output goes to block K + 1's ring (row slot
+// oy & 3) or, for K = 5, to HBM; zero: the bottom padding row (zeros).
 // DWR: the depthwise table of the lane's channel quads in registers (dwr, bff_dwload) instead of
 // 10 ds_read_b128 per K-step from the LDS copy (the front is LDS-bandwidth-bound).  NC0 / NC: the
 // output-channel chunks this wave computes (two waves may share a row, each with its own chunks:
@@ -1327,41 +1249,30 @@ __device__ __forceinline__ void bff_block(float* lds, int oy, int c, bool zero,
       const int c0 = 4 * half + 8 * k;
       f32x4 av = DWR ? dwr[k][9] : ld4(dwt + 9 * L::CINP + c0);
 #pragma unroll
-      for (int tp = 0; tp < 9; ++tp) {
-        const float* rp = tp < 3 ? r0 : (tp < 6 ? r1 : r2);
-        const f32x4 xv = ld4(rp + (tp % 3) * L::CS + c0);
-        const f32x4 wv = DWR ? dwr[k][tp] : ld4(dwt + tp * L::CINP + c0);
-        av.x = fmaf(xv.x, wv.x, av.x);
-        av.y = fmaf(xv.y, wv.y, av.y);
-        av.z = fmaf(xv.z, wv.z, av.z);
-        av.w = fmaf(xv.w, wv.w, av.w);
-      }
+      for (int tp = 0; tp < 9; ++tp)  // dw_quad's loop (see there)
+        av = dw_tap(av, ld4((tp < 3 ? r0 : (tp < 6 ? r1 : r2)) + (tp % 3) * L::CS + c0),
+                    DWR ? dwr[k][tp] : ld4(dwt + tp * L::CINP + c0));
 #pragma unroll
       for (int nc = 0; nc < NC; ++nc) acc[nc] = mfma_split(av, wr[nc][k], acc[nc]);
     }
   }
-  // epilogue: lane = output channel, register g = position 32 c + 4 half + (g & 3) + 8 (g >> 2).
+  // epilogue: lane = output channel, register g = position 32 c + acc_pos(g, half).
   // Every residual read of the row is issued before the first output write: the writes go to the
   // next layer's ring in the same LDS array, which the compiler cannot tell apart from this ring, so
   // read-write-read-... interleaved put each read behind its own lgkmcnt(0) (an LDS round trip per
   // output register; round 6)
-#ifndef BFF_RESB
-#define BFF_RESB 1
-#endif
   float res[NC][16];
-  if (BFF_RESB && !zero) {
+  if (!zero) {
 #pragma unroll
     for (int nc = 0; nc < NC; ++nc) {
       const int n = min((NC0 + nc) * 32 + l32, L::CINP - 1);  // n >= CINP: read a valid address, unused
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int x = 32 * c + 4 * half + (g & 3) + 8 * (g >> 2);
+        const int x = 32 * c + acc_pos(g, half);
         if (L::S == 1) {
           res[nc][g] = ring[(oy & 3) * ROW + (x + L::PADL) * L::CS + n];
-        } else {
-          const float* t0 = ring + ((2 * oy) & 3) * ROW + 2 * x * L::CS + n;
-          const float* t1 = ring + ((2 * oy + 1) & 3) * ROW + 2 * x * L::CS + n;
-          res[nc][g] = fmaxf(fmaxf(t0[0], t0[L::CS]), fmaxf(t1[0], t1[L::CS]));
+        } else {  // rows 2 oy, 2 oy + 1: an even row's ring slot is 0 or 2, the next row is the next slot
+          res[nc][g] = max_pool2(ring + ((2 * oy) & 3) * ROW + 2 * x * L::CS + n, L::CS, ROW);
         }
       }
     }
@@ -1372,21 +1283,11 @@ __device__ __forceinline__ void bff_block(float* lds, int oy, int c, bool zero,
     if (n >= L::COUTP) continue;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int x = 32 * c + 4 * half + (g & 3) + 8 * (g >> 2);
+      const int x = 32 * c + acc_pos(g, half);
       float v = 0.f;
       if (!zero) {
         v = acc[nc][g] + bias[nc];
-        if (n < L::CINP) {
-          if (BFF_RESB) {
-            v += res[nc][g];
-          } else if (L::S == 1) {
-            v += ring[(oy & 3) * ROW + (x + L::PADL) * L::CS + n];
-          } else {
-            const float* t0 = ring + ((2 * oy) & 3) * ROW + 2 * x * L::CS + n;
-            const float* t1 = ring + ((2 * oy + 1) & 3) * ROW + 2 * x * L::CS + n;
-            v += fmaxf(fmaxf(t0[0], t0[L::CS]), fmaxf(t1[0], t1[L::CS]));
-          }
-        }
+        if (n < L::CINP) v += res[nc][g];
         v = v > 0.f ? v : 0.f;
       }
       if constexpr (K < 5) {
@@ -1432,28 +1333,11 @@ __global__ void __launch_bounds__(BFF_NW * 64) bf_front_kernel(BfFrontArgs a) {
   };
 
   if (wave < 2) {
-    // ---- stem (bf_stem_kernel's arithmetic): 32 positions ox = 32 wave + l32 of row p ----
+    // ---- stem (stem_weights + stem_k, as bf_stem_kernel): 32 positions ox = 32 wave + l32 of row p ----
     const int* f = a.stem;
     SplitW wsp[STEM_NK];
     float inv;
-    {
-      f32x8 v[STEM_NK];
-      float mx = 0.f;
-#pragma unroll
-      for (int s = 0; s < STEM_NK; ++s) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int q = 8 * s + j;
-          v[s][j] = q < STEM_KS ? P_[f[BFO_PWW] + l32 * 90 + half * STEM_KS + q] : 0.f;
-          mx = fmaxf(mx, fabsf(v[s][j]));
-        }
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float s1 = pow2_scale(mx, 13);
-      inv = SPLIT_INV_C / s1;
-#pragma unroll
-      for (int s = 0; s < STEM_NK; ++s) wsp[s] = split_w8(v[s] * s1);
-    }
+    stem_weights(P_, f[BFO_PWW], l32, half, wsp, inv);
     const int cout = f[BFO_COUT];
     const float bias = l32 < cout ? P_[f[BFO_PWB] + l32] : 0.f;
     for (int64_t img = blockIdx.x; img < a.nimg; img += gridDim.x) {
@@ -1468,23 +1352,14 @@ __global__ void __launch_bounds__(BFF_NW * 64) bf_front_kernel(BfFrontArgs a) {
             const float* tr[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) tr[k] = lds + BFF_IN + ((2 * p - 1 + 3 * half + k + BFF_NIN) % BFF_NIN) * BFF_INS + 1 + 6 * ox;
-#pragma unroll
-            for (int s = 0; s < STEM_NK; ++s) {
-              f32x8 xv;
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const int q = 8 * s + j;
-                xv[j] = q < STEM_KS ? tr[q / 15][((q / 3) % 5) * 3 + q % 3] : 0.f;
-              }
-              acc = mfma3_dw(split_d8(xv), wsp[s], acc);
-            }
+            acc = stem_k(tr[0], tr[1], tr[2], wsp);
           }
           if (l32 < cout) {
             using O = BffL<1>;
             float* drow = lds + O::RING + (p & 3) * (O::COLS * O::CS) + O::PADL * O::CS + l32;
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-              const int x = 32 * wave + 4 * half + (g & 3) + 8 * (g >> 2);
+              const int x = 32 * wave + acc_pos(g, half);
               float v = 0.f;
               if (p < 64) {
                 v = fmaf(acc[g], inv, bias);
@@ -1497,7 +1372,8 @@ __global__ void __launch_bounds__(BFF_NW * 64) bf_front_kernel(BfFrontArgs a) {
         BFF_BAR();
       }
     }
-  } else if (wave == 2 || (wave == 3 && !BFF_SPLIT45)) {
+  } else if (wave == 2) {
+    // block 1, both chunks of a row
     f32x4 wr[1][3], dwr[3][10];
     float bias[1];
     bff_wload<1>(a, wr, bias, l32, half);
@@ -1507,8 +1383,8 @@ __global__ void __launch_bounds__(BFF_NW * 64) bf_front_kernel(BfFrontArgs a) {
       for (int p = 0; p < BFF_PHASES; ++p) {
         const int oy = p - 2;
         if (oy >= 0 && oy <= 64) {
-          bff_block<1, true>(lds, oy, wave - 2, oy == 64, wr, bias, nullptr, l32, half, dwr);
-          if (BFF_SPLIT45) bff_block<1, true>(lds, oy, 1, oy == 64, wr, bias, nullptr, l32, half, dwr);
+          bff_block<1, true>(lds, oy, 0, oy == 64, wr, bias, nullptr, l32, half, dwr);
+          bff_block<1, true>(lds, oy, 1, oy == 64, wr, bias, nullptr, l32, half, dwr);
         }
         BFF_BAR();
       }
@@ -1586,20 +1462,20 @@ __global__ void __launch_bounds__(BFF_NW * 64) bf_front_kernel(BfFrontArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
   } else {
-    constexpr int N45 = BFF_SPLIT45 ? 1 : 2;
-    f32x4 w4[N45][4], w5[N45][5];
-    float b4[N45], b5[N45];
-    bff_wload<4, 0, N45>(a, w4, b4, l32, half);
-    bff_wload<5, 0, N45>(a, w5, b5, l32, half);
+    // blocks 4 / 5's first output-channel chunk
+    f32x4 w4[1][4], w5[1][5];
+    float b4[1], b5[1];
+    bff_wload<4, 0, 1>(a, w4, b4, l32, half);
+    bff_wload<5, 0, 1>(a, w5, b5, l32, half);
     for (int64_t img = blockIdx.x; img < a.nimg; img += gridDim.x) {
       frame_begin(img);
       float* gout = a.dst + img * (32 * 32 * 48);
       for (int p = 0; p < BFF_PHASES; ++p) {
         if (p & 1) {
-          if (p >= 13) bff_block<5, false, 0, N45>(lds, (p - 13) >> 1, 0, false, w5, b5, gout, l32, half);
+          if (p >= 13) bff_block<5, false, 0, 1>(lds, (p - 13) >> 1, 0, false, w5, b5, gout, l32, half);
         } else {
           const int oy = (p - 10) >> 1;
-          if (p >= 10 && oy <= 32) bff_block<4, false, 0, N45>(lds, oy, 0, oy == 32, w4, b4, nullptr, l32, half);
+          if (p >= 10 && oy <= 32) bff_block<4, false, 0, 1>(lds, oy, 0, oy == 32, w4, b4, nullptr, l32, half);
         }
         BFF_BAR();
       }
@@ -1626,15 +1502,6 @@ static int bfs_nc(int nchunk, int nct) {
   for (int nc = 1; nc <= nct && nc <= BFS_MAXNC; ++nc)
     if (nct % nc == 0 && nchunk * (nct / nc) <= BFS_NW) return nc;
   return 0;
-}
-// the NC a stage op runs with: BFS_NCMAX prefers the most output-channel chunks per task (fewer
-// tasks, the depthwise work done once per position chunk) over the most busy waves
-static int bfs_nc_run(int nchunk, int nct) {
-#ifdef BFS_NCMAX
-  for (int nc = nct < BFS_MAXNC ? nct : BFS_MAXNC; nc >= 1; --nc)
-    if (nct % nc == 0 && nchunk * (nct / nc) <= BFS_NW) return nc;
-#endif
-  return bfs_nc(nchunk, nct);
 }
 
 // the task variant of stage op k (record g); the band op (the first op, s2 onto a 16x16 map) also
@@ -1684,7 +1551,8 @@ static int check_stage(const int* f, int i, int rest) {
     if (dw ? (g[BFO_RES] != BF_RES_ID && g[BFO_RES] != BF_RES_MAXPOOL) || !g[BFO_RELU] : g[BFO_RELU])
       return hpe_fail(HPE_EINVAL, "blazeface stage %d op %d: residual / ReLU variant", i, k);
     if ((g[BFO_RES] == BF_RES_MAXPOOL && (s != 2 || h != 2 * ho || w != 2 * wo || g[BFO_PADT] || g[BFO_PADL])) ||
-        (g[BFO_RES] == BF_RES_ID && (s != 1 || h != ho || w != wo)))
+        // s1 tasks leave the row taps (BFV_DPP16 every tap) unmasked: they count on pad (1, 1) and the halo rows
+        (g[BFO_RES] == BF_RES_ID && (s != 1 || h != ho || w != wo || g[BFO_PADT] != 1 || g[BFO_PADL] != 1)))
       return hpe_fail(HPE_EINVAL, "blazeface stage %d op %d: stride / residual geometry", i, k);
     if (k == 0) {
       if (!dw || g[BFO_SRC] == BF_BUF_IMG) return hpe_fail(HPE_EINVAL, "blazeface stage %d: must start with a block reading a map", i);
@@ -1751,65 +1619,86 @@ static int check_front(const int* f, int i, int rest) {
   return 0;
 }
 
-static int check_op(const int* f, int i, int rest) {
-  const int kind = f[BFO_KIND];
-  if (kind == BF_STAGE) return check_stage(f, i, rest);
-  if (kind == BF_FRONT) return check_front(f, i, rest);
-  if (kind != BF_STEM && kind != BF_BLOCK && kind != BF_ROWS && kind != BF_DIRECT) return hpe_fail(HPE_EINVAL, "blazeface op %d: bad kind %d", i, kind);
-  if (kind == BF_DIRECT) {
-    const int s = f[BFO_STRIDE], dw = f[BFO_DW], wo = f[BFO_WO], ho = f[BFO_HO];
-    if (!pick_direct(s, dw, f[BFO_NC]) || f[BFO_NC] != f[BFO_NCT]) return hpe_fail(HPE_EINVAL, "blazeface op %d: no direct kernel S=%d DW=%d NC=%d", i, s, dw, f[BFO_NC]);
-    if (wo <= 0 || (wo & (wo - 1)) || (ho * wo) % 32) return hpe_fail(HPE_EINVAL, "blazeface op %d: direct kernel needs Wo a power of two, Ho*Wo % 32 == 0", i);
-    if (f[BFO_WAVES] < 1 || f[BFO_WAVES] > 4) return hpe_fail(HPE_EINVAL, "blazeface op %d: waves", i);
-    if (f[BFO_CINP] % 8 || f[BFO_CINP] < f[BFO_CIN] || f[BFO_COUTP] % 8 || f[BFO_COUTP] < f[BFO_COUT] ||
-        f[BFO_KS] < f[BFO_CINP] || f[BFO_KS] % 4 || f[BFO_NCT] < 1 || f[BFO_NCT] * 32 < f[BFO_COUTP])
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
-    if (dw ? (s == 1 ? (f[BFO_H] != ho || f[BFO_W] != wo || f[BFO_PADT] != 1 || f[BFO_PADL] != 1)
-                     : (f[BFO_H] != 2 * ho || f[BFO_W] != 2 * wo || f[BFO_PADT] || f[BFO_PADL]))
-           : (f[BFO_H] != ho || f[BFO_W] != wo || s != 1))
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: direct kernel map geometry", i);
-    if ((f[BFO_RES] == BF_RES_MAXPOOL && s != 2) || (f[BFO_RES] == BF_RES_ID && s != 1))
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: residual / stride", i);
-    const long need = 4L * (f[BFO_NCT] * 32 * f[BFO_KS] + (dw ? 10 * f[BFO_CINP] : 0));
-    if (f[BFO_LDS] < need || f[BFO_LDS] > 160 * 1024) return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS", i);
-    if (f[BFO_SRC] < 0 || f[BFO_SRC] >= BF_NBUF || f[BFO_DST] < 0 || f[BFO_DST] >= BF_NBUF) return hpe_fail(HPE_EINVAL, "blazeface op %d: bad buffer", i);
-    if (!f[BFO_SPLIT] && (f[BFO_OSTRIDE] < f[BFO_COUT] || f[BFO_OSTRIDE] > f[BFO_COUTP]))
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: output stride", i);
-    if (f[BFO_SPLIT] && (f[BFO_DST2] < 0 || f[BFO_DST2] >= BF_NBUF || f[BFO_SPLIT] >= f[BFO_COUT]))
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: bad split", i);
-    return 0;
-  }
-  if (kind == BF_ROWS) {
-    const int S = f[BFO_STRIDE], R = f[BFO_TH], nseg = f[BFO_NI], kq = f[BFO_CINP] / 4;
-    if (!pick_rows_op(f) || !f[BFO_DW] || f[BFO_SPLIT] || !f[BFO_RELU]) return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel variant", i);
-    if (f[BFO_WAVES] < 1 || f[BFO_WAVES] > 4) return hpe_fail(HPE_EINVAL, "blazeface op %d: waves", i);
-    if (R <= 0 || nseg <= 0 || f[BFO_HO] % nseg || (f[BFO_HO] / nseg) % R) return hpe_fail(HPE_EINVAL, "blazeface op %d: row steps", i);
-    const int wo = f[BFO_WO];
-    if (wo < 16 || (wo & (wo - 1)) || (R * wo) % 32) return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel needs Wo >= 16, a power of two", i);
-    if (f[BFO_ROWS] != (R - 1) * S + 3 || f[BFO_COLS] != (wo - 1) * S + 3) return hpe_fail(HPE_EINVAL, "blazeface op %d: ring geometry", i);
-    if (S == 1 ? (f[BFO_PADT] != 1 || f[BFO_PADL] != 1 || f[BFO_RES] != BF_RES_ID || f[BFO_H] != f[BFO_HO] || f[BFO_W] != wo)
-               : (f[BFO_PADT] || f[BFO_PADL] || f[BFO_RES] != BF_RES_MAXPOOL || f[BFO_H] != 2 * f[BFO_HO] || f[BFO_W] != 2 * wo))
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel stride/padding/residual", i);
-    if (R * S * f[BFO_W] * kq > RPF * 64 * f[BFO_WAVES]) return hpe_fail(HPE_EINVAL, "blazeface op %d: prefetch share exceeds %d float4/thread", i, RPF);
-    if (f[BFO_CINP] % 8 || f[BFO_CS] < f[BFO_CINP] || f[BFO_CS] % 4 || f[BFO_KS] < f[BFO_CINP] || f[BFO_KS] % 4 ||
-        f[BFO_NCT] < 1 || f[BFO_NCT] * 32 < f[BFO_COUTP] || f[BFO_NCT] % f[BFO_NC] || f[BFO_OSTRIDE] < f[BFO_COUT] ||
-        f[BFO_OSTRIDE] > f[BFO_COUTP] || f[BFO_COUTP] % 8)
-      return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
-    const long need = 4L * (f[BFO_NCT] * 32 * f[BFO_KS] + 10 * f[BFO_CINP] + (long)f[BFO_ROWS] * f[BFO_COLS] * f[BFO_CS]);
-    if (f[BFO_LDS] < need || f[BFO_LDS] > 160 * 1024) return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS", i);
-    if (f[BFO_SRC] < 0 || f[BFO_SRC] >= BF_NBUF || f[BFO_DST] < 0 || f[BFO_DST] >= BF_NBUF) return hpe_fail(HPE_EINVAL, "blazeface op %d: bad buffer", i);
-    return 0;
-  }
+// ---- checks the single-op records (direct, rows, stem / block) share ----
+static int check_bufs(const int* f, int i) {
+  if (f[BFO_SRC] < 0 || f[BFO_SRC] >= BF_NBUF || f[BFO_DST] < 0 || f[BFO_DST] >= BF_NBUF)
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: bad buffer", i);
+  return 0;
+}
+static int check_waves(const int* f, int i, int max) {
+  if (f[BFO_WAVES] < 1 || f[BFO_WAVES] > max) return hpe_fail(HPE_EINVAL, "blazeface op %d: waves", i);
+  return 0;
+}
+// padded channel counts (multiples of 8 that cover the real ones), the W^T row stride and, for the
+// kernels with an LDS tile or ring (cs), its channel stride
+static bool bad_channels(const int* f, bool cs) {
+  return f[BFO_CINP] % 8 || f[BFO_CINP] < f[BFO_CIN] || f[BFO_COUTP] % 8 || f[BFO_COUTP] < f[BFO_COUT] ||
+         f[BFO_KS] < f[BFO_CINP] || f[BFO_KS] % 4 || (cs && (f[BFO_CS] < f[BFO_CINP] || f[BFO_CS] % 4));
+}
+// output-channel chunks of 32 that cover COUTP, in whole groups of NC
+static bool bad_chunks(const int* f) {
+  return f[BFO_NCT] < 1 || f[BFO_NCT] * 32 < f[BFO_COUTP] || f[BFO_NC] < 1 || f[BFO_NCT] % f[BFO_NC];
+}
+static bool bad_ostride(const int* f) { return f[BFO_OSTRIDE] < f[BFO_COUT] || f[BFO_OSTRIDE] > f[BFO_COUTP]; }
+// one output buffer at stride OSTRIDE, or the channels split over two
+static int check_out(const int* f, int i) {
+  if (!f[BFO_SPLIT] && bad_ostride(f)) return hpe_fail(HPE_EINVAL, "blazeface op %d: output stride", i);
+  if (f[BFO_SPLIT] && (f[BFO_DST2] < 0 || f[BFO_DST2] >= BF_NBUF || f[BFO_SPLIT] >= f[BFO_COUT]))
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: bad split", i);
+  return 0;
+}
+// LDS bytes: W^T, the depthwise table and `map` floats of tile / ring
+static long lds_need(const int* f, long map) {
+  return 4L * (f[BFO_NCT] * 32 * f[BFO_KS] + (f[BFO_DW] ? 10 * f[BFO_CINP] : 0) + map);
+}
+
+static int check_direct(const int* f, int i) {
+  const int s = f[BFO_STRIDE], dw = f[BFO_DW], wo = f[BFO_WO], ho = f[BFO_HO];
+  if (!pick_direct(s, dw, f[BFO_NC]) || f[BFO_NC] != f[BFO_NCT]) return hpe_fail(HPE_EINVAL, "blazeface op %d: no direct kernel S=%d DW=%d NC=%d", i, s, dw, f[BFO_NC]);
+  if (wo <= 0 || (wo & (wo - 1)) || (ho * wo) % 32) return hpe_fail(HPE_EINVAL, "blazeface op %d: direct kernel needs Wo a power of two, Ho*Wo % 32 == 0", i);
+  if (int rc = check_waves(f, i, 4)) return rc;
+  if (bad_channels(f, false) || bad_chunks(f)) return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
+  if (dw ? (s == 1 ? (f[BFO_H] != ho || f[BFO_W] != wo || f[BFO_PADT] != 1 || f[BFO_PADL] != 1)
+                   : (f[BFO_H] != 2 * ho || f[BFO_W] != 2 * wo || f[BFO_PADT] || f[BFO_PADL]))
+         : (f[BFO_H] != ho || f[BFO_W] != wo || s != 1))
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: direct kernel map geometry", i);
+  if ((f[BFO_RES] == BF_RES_MAXPOOL && s != 2) || (f[BFO_RES] == BF_RES_ID && s != 1))
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: residual / stride", i);
+  if (f[BFO_LDS] < lds_need(f, 0) || f[BFO_LDS] > 160 * 1024) return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS", i);
+  if (int rc = check_bufs(f, i)) return rc;
+  return check_out(f, i);
+}
+
+static int check_rows(const int* f, int i) {
+  const int S = f[BFO_STRIDE], R = f[BFO_TH], nseg = f[BFO_NI], kq = f[BFO_CINP] / 4;
+  if (!pick_rows_op(f) || !f[BFO_DW] || f[BFO_SPLIT] || !f[BFO_RELU]) return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel variant", i);
+  if (int rc = check_waves(f, i, 4)) return rc;
+  if (R <= 0 || nseg <= 0 || f[BFO_HO] % nseg || (f[BFO_HO] / nseg) % R) return hpe_fail(HPE_EINVAL, "blazeface op %d: row steps", i);
+  const int wo = f[BFO_WO];
+  if (wo < 16 || (wo & (wo - 1)) || (R * wo) % 32) return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel needs Wo >= 16, a power of two", i);
+  if (f[BFO_ROWS] != (R - 1) * S + 3 || f[BFO_COLS] != (wo - 1) * S + 3) return hpe_fail(HPE_EINVAL, "blazeface op %d: ring geometry", i);
+  if (S == 1 ? (f[BFO_PADT] != 1 || f[BFO_PADL] != 1 || f[BFO_RES] != BF_RES_ID || f[BFO_H] != f[BFO_HO] || f[BFO_W] != wo)
+             : (f[BFO_PADT] || f[BFO_PADL] || f[BFO_RES] != BF_RES_MAXPOOL || f[BFO_H] != 2 * f[BFO_HO] || f[BFO_W] != 2 * wo))
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: rows kernel stride/padding/residual", i);
+  if (R * S * f[BFO_W] * kq > RPF * 64 * f[BFO_WAVES]) return hpe_fail(HPE_EINVAL, "blazeface op %d: prefetch share exceeds %d float4/thread", i, RPF);
+  if (bad_channels(f, true) || bad_chunks(f) || bad_ostride(f)) return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
+  if (f[BFO_LDS] < lds_need(f, (long)f[BFO_ROWS] * f[BFO_COLS] * f[BFO_CS]) || f[BFO_LDS] > 160 * 1024)
+    return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS", i);
+  return check_bufs(f, i);
+}
+
+// stem and block: one LDS tile (+ halo) of TH output rows, or NI whole images, per workgroup
+static int check_tile(const int* f, int i) {
+  const bool stem = f[BFO_KIND] == BF_STEM;
   if (f[BFO_TH] <= 0 || f[BFO_NI] <= 0 || f[BFO_HO] % f[BFO_TH]) return hpe_fail(HPE_EINVAL, "blazeface op %d: bad tile", i);
   if ((f[BFO_NI] * f[BFO_TH] * f[BFO_WO]) % 32) return hpe_fail(HPE_EINVAL, "blazeface op %d: tile not a multiple of 32 positions", i);
   if (f[BFO_NI] > 1 && f[BFO_TH] != f[BFO_HO]) return hpe_fail(HPE_EINVAL, "blazeface op %d: multi-image tiles must be whole images", i);
   if (f[BFO_LDS] <= 0 || f[BFO_LDS] > 160 * 1024) return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS %d bytes", i, f[BFO_LDS]);
-  if (f[BFO_SRC] < 0 || f[BFO_SRC] >= BF_NBUF || f[BFO_DST] < 0 || f[BFO_DST] >= BF_NBUF)
-    return hpe_fail(HPE_EINVAL, "blazeface op %d: bad buffer", i);
+  if (int rc = check_bufs(f, i)) return rc;
   const int wo = f[BFO_WO], ppi = f[BFO_TH] * f[BFO_WO];
   if (wo <= 0 || (wo & (wo - 1)) || (ppi & (ppi - 1))) return hpe_fail(HPE_EINVAL, "blazeface op %d: Wo and TH*Wo must be powers of two", i);
-  if (f[BFO_WAVES] < 1 || f[BFO_WAVES] > (kind == BF_STEM ? 4 : 8)) return hpe_fail(HPE_EINVAL, "blazeface op %d: waves", i);
-  if (kind == BF_STEM) {
+  if (int rc = check_waves(f, i, stem ? 4 : 8)) return rc;
+  if (stem) {
     if (f[BFO_CIN] != 3 || f[BFO_COUT] > 32 || f[BFO_STRIDE] != 2) return hpe_fail(HPE_EINVAL, "blazeface stem: unsupported geometry");
     const int rows = 2 * (f[BFO_TH] - 1) + 6, cols = 2 * (f[BFO_WO] - 1) + 5;
     if (f[BFO_ROWS] != rows || f[BFO_COLS] != cols || f[BFO_LDS] < rows * cols * 12)
@@ -1817,26 +1706,30 @@ static int check_op(const int* f, int i, int rest) {
     return 0;
   }
   const int s = f[BFO_STRIDE], dw = f[BFO_DW];
-  if (f[BFO_NCT] < 1 || f[BFO_NCT] * 32 < f[BFO_COUTP] || f[BFO_NCT] % f[BFO_NC] || f[BFO_CINP] / 4 > 64 * f[BFO_WAVES])
-    return hpe_fail(HPE_EINVAL, "blazeface op %d: channel chunks", i);
+  if (bad_chunks(f) || f[BFO_CINP] / 4 > 64 * f[BFO_WAVES]) return hpe_fail(HPE_EINVAL, "blazeface op %d: channel chunks", i);
   if (!pick_block(s, dw, f[BFO_NC])) return hpe_fail(HPE_EINVAL, "blazeface op %d: no kernel for S=%d DW=%d NC=%d", i, s, dw, f[BFO_NC]);
-  if (f[BFO_CINP] % 8 || f[BFO_CINP] < f[BFO_CIN] || f[BFO_COUTP] % 8 || f[BFO_COUTP] < f[BFO_COUT] ||
-      f[BFO_CS] < f[BFO_CINP] || f[BFO_CS] % 4 || f[BFO_KS] < f[BFO_CINP] || f[BFO_KS] % 4)
-    return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
+  if (bad_channels(f, true)) return hpe_fail(HPE_EINVAL, "blazeface op %d: channel geometry", i);
   const int rows = dw ? (f[BFO_TH] - 1) * s + 3 : f[BFO_TH];
   const int cols = dw ? (f[BFO_WO] - 1) * s + 3 : f[BFO_WO];
   if (f[BFO_ROWS] != rows || f[BFO_COLS] != cols) return hpe_fail(HPE_EINVAL, "blazeface op %d: tile rows/cols", i);
   if (f[BFO_RES] == BF_RES_MAXPOOL && (s != 2 || f[BFO_H] % 2 || f[BFO_W] % 2 || f[BFO_PADT] || f[BFO_PADL]))
     return hpe_fail(HPE_EINVAL, "blazeface op %d: maxpool residual needs s2 on even maps", i);
   if (f[BFO_RES] == BF_RES_ID && s != 1) return hpe_fail(HPE_EINVAL, "blazeface op %d: identity residual needs s1", i);
-  const long need = 4L * (f[BFO_NCT] * 32 * f[BFO_KS] + (dw ? 10 * f[BFO_CINP] : 0) +
-                          (long)f[BFO_NI] * rows * cols * f[BFO_CS]);
+  const long need = lds_need(f, (long)f[BFO_NI] * rows * cols * f[BFO_CS]);
   if (f[BFO_LDS] < need) return hpe_fail(HPE_EINVAL, "blazeface op %d: LDS words %d < %ld", i, f[BFO_LDS], need);
-  if (!f[BFO_SPLIT] && (f[BFO_OSTRIDE] < f[BFO_COUT] || f[BFO_OSTRIDE] > f[BFO_COUTP]))
-    return hpe_fail(HPE_EINVAL, "blazeface op %d: output stride", i);
-  if (f[BFO_SPLIT] && (f[BFO_DST2] < 0 || f[BFO_DST2] >= BF_NBUF || f[BFO_SPLIT] >= f[BFO_COUT]))
-    return hpe_fail(HPE_EINVAL, "blazeface op %d: bad split", i);
-  return 0;
+  return check_out(f, i);
+}
+
+static int check_op(const int* f, int i, int rest) {
+  switch (f[BFO_KIND]) {
+    case BF_STAGE: return check_stage(f, i, rest);
+    case BF_FRONT: return check_front(f, i, rest);
+    case BF_DIRECT: return check_direct(f, i);
+    case BF_ROWS: return check_rows(f, i);
+    case BF_STEM:
+    case BF_BLOCK: return check_tile(f, i);
+    default: return hpe_fail(HPE_EINVAL, "blazeface op %d: bad kind %d", i, f[BFO_KIND]);
+  }
 }
 
 extern "C" int hpe_blazeface_create(const int32_t* words, int64_t n_words, hpe_blazeface** out) {
@@ -1928,7 +1821,7 @@ extern "C" int hpe_blazeface_forward(const hpe_blazeface* h, const float* params
         BfSub& o = sa.op[k];
         o.s = g[BFO_STRIDE]; o.h = g[BFO_H]; o.w = g[BFO_W]; o.ho = g[BFO_HO]; o.wo = g[BFO_WO];
         o.cin = g[BFO_CIN]; o.cinp = g[BFO_CINP]; o.cout = g[BFO_COUT]; o.coutp = g[BFO_COUTP];
-        o.ks = g[BFO_KS]; o.nct = g[BFO_NCT]; o.nc = bfs_nc_run((o.ho * o.wo) >> 5, o.nct);
+        o.ks = g[BFO_KS]; o.nct = g[BFO_NCT]; o.nc = bfs_nc((o.ho * o.wo) >> 5, o.nct);
         o.res = g[BFO_RES]; o.relu = g[BFO_RELU]; o.dw = g[BFO_DW]; o.padt = g[BFO_PADT]; o.padl = g[BFO_PADL];
         o.dww = g[BFO_DWW]; o.pww = g[BFO_PWW]; o.pwb = g[BFO_PWB];
         o.var = bfs_variant(g, k, sa.map_floats, sa.wt_floats, &o.wto, &o.sst, &o.nc);
@@ -1970,14 +1863,12 @@ extern "C" int hpe_blazeface_forward(const hpe_blazeface* h, const float* params
       const int64_t tasks = n_images * ((f[BFO_HO] * f[BFO_WO]) >> 5);
       int per_cu = (160 * 1024) / f[BFO_LDS];
       if (per_cu > 12 / f[BFO_WAVES]) per_cu = 12 / f[BFO_WAVES];
-#ifndef BF_NO_OCC
       // resident workgroups as the runtime counts them (VGPRs + AGPRs, LDS): a grid sized past
       // them runs its tasks in a second, partial round
       int res = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&res, (const void*)k, threads, f[BFO_LDS]) == hipSuccess &&
           res > 0 && per_cu > res)
         per_cu = res;
-#endif
       if (per_cu < 1) per_cu = 1;
       nwg = (tasks + f[BFO_WAVES] - 1) / f[BFO_WAVES];
       if (nwg > (int64_t)h->n_cu * per_cu) nwg = (int64_t)h->n_cu * per_cu;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Fast variant library for A/B runs: the in-tree objects with ONE translation unit recompiled
-# under extra flags (e.g. -DBFS_PIPE=1), linked to varlibs/libhpe_<name>.so.
+# under extra flags (e.g. -DBFS_STAMPS), linked to varlibs/libhpe_<name>.so.
 # Usage: scripts/build_variant_obj.sh <name> <unit.hip> -- <extra hipcc flags>
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

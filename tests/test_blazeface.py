@@ -197,6 +197,15 @@ def test_capi_validates_stage_record():
         bad = words.copy()
         bad[base + field] = val
         assert lib.hpe_blazeface_create(bad.ctypes.data_as(ctypes.c_void_p), bad.size, ctypes.byref(h)) == 1, field
+    # an s1 block of the stage with other padding than (1, 1): its tasks leave the row taps unmasked
+    # and count on the map's zero halo rows
+    s1 = [j for j in range(k + 1, k + 1 + int(recs[k][B.BFO_NI]))
+          if recs[j][B.BFO_DW] and recs[j][B.BFO_STRIDE] == 1][0]
+    assert recs[s1][B.BFO_RES] == B.RES_ID and recs[s1][B.BFO_PADT] == 1 and recs[s1][B.BFO_PADL] == 1
+    for field in (B.BFO_PADT, B.BFO_PADL):
+        bad = words.copy()
+        bad[B.BFH_WORDS + s1 * B.BFO_WORDS + field] = 0
+        assert lib.hpe_blazeface_create(bad.ctypes.data_as(ctypes.c_void_p), bad.size, ctypes.byref(h)) == 1, field
     # the first 8x8 head moved before the block that writes its tap
     bad = words.copy()
     a, b = base + 12 * B.BFO_WORDS, base + 13 * B.BFO_WORDS
