@@ -63,8 +63,11 @@ struct E2 {
 // division per row; at P >= 32 a tile straddles at most one image boundary)
 struct TileImg {
   int img0, rem0, P;
+  // P32: P >= 32 known at compile time (the contiguous-rows instantiation: no division path)
+  template <bool P32 = false>
   __device__ __forceinline__ int of(int r) const {
     const int t = rem0 + r;
+    if (P32) return img0 + (t >= P ? 1 : 0);
     return img0 + (P >= 32 ? (t >= P ? 1 : 0) : (P == 1 ? t : t / P));
   }
   // advance by S rows, (dq, dr) = divmod(S, P) precomputed
@@ -143,6 +146,40 @@ __device__ __forceinline__ void stage_tile(const Args& args, float* xs, float* l
   }
 }
 
+// the lane id recomputed where it is used (two VALU ops) instead of a value hoisted to kernel entry:
+// a kernel at its register budget spills such lane constants around its tile loop, and the reload's
+// vmcnt(0) waits for every LDS-DMA piece in flight
+__device__ __forceinline__ int lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// Staging of the contiguous-rows instantiation (no gather, P >= 32; mlp2_kernel<..., CONTIG>): tp is
+// the tile's first row in HBM, carried by the tile loop (no 64-bit row * C_in product per piece), ti
+// its image; one piece per row at the padded stride, as stage_tile's contiguous path.  (Twelve packed
+// 1-KiB pieces per full 96-channel tile at the row stride 96 measured the same step time, A/B x3 on
+// MI355X, and are not kept.)
+__device__ __forceinline__ void stage_contig(const Args& args, float* xs, float* lab, const float* tp,
+                                             int64_t row0, const TileImg& ti, int wave, int NCB, int Cin,
+                                             bool labels) {
+  const int lane = lane_now();
+  const int64_t rem = args.nrows - 1 - row0;
+  const int last = rem < 31 ? (int)rem : 31;
+  if (labels && wave == 0) {
+    const float* yp = args.ytrue + (int64_t)ti.img0 * 3;
+#pragma unroll
+    for (int pc = 0; pc < 2; ++pc) {
+      const int slot = pc * 64 + lane;
+      const int r = min(slot >> 2, last), j = min(slot & 3, 2);
+      glds4(yp + (ti.rem0 + r >= ti.P ? 3 + j : j), lds_addr(lab + pc * 64));
+    }
+  }
+  const int q = Cin >> 2;
+  for (int r = wave; r < 32; r += NCB)
+    if (lane < q) glds16(tp + min(r, last) * Cin + 4 * lane, lds_addr(xs + r * MLP2_XS));
+}
+
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // One split of the landed X tile per workgroup instead of one per wave (the 12 waves all read the
@@ -169,11 +206,21 @@ __device__ __forceinline__ void split_d4(f32x4 v, h4& ch, h4& cl, h4& h) {
 // padding is the least that gives 16 distinct start quads; the rows' b32 stores / reads stay
 // contiguous, and a1_row(g) of an unrolled g is an immediate offset
 __device__ __forceinline__ constexpr int a1_row(int g) { return 68 * (g ^ ((g >> 1) & 4)); }
+// Returns the data side of the split kernels' overflow guard: whether a value of the tile lies
+// outside the fp16 range of its fragment ch = fp16(C x), i.e. !(|x| < 65520 / C) — a round-to-nearest
+// fp16 conversion gives infinity from 65520 on.  With finite W1 fragments (the prologue checks the
+// scaled values it splits) that is exactly when the forward accumulator of the tile is non-finite:
+// an in-range tile accumulates 3 x 96 products of finite fp16 fragments, and an infinite ch, or a
+// NaN, reaches every column's accumulator of its row (0 x inf = NaN), the zero pad columns' too.
+#define MLP2_X_LIMIT (65520.f / SPLIT_C)
 template <int KH>
-__device__ __forceinline__ void presplit_tile(const float* xs, _Float16* xf, _Float16* xt, int tid, int NT) {
+__device__ __forceinline__ bool presplit_tile(const float* xs, _Float16* xf, _Float16* xt, int tid, int NT) {
+  bool out = false;
   for (int i = tid; i < 32 * 24; i += NT) {
     const int r = i / 24, rem = i - r * 24, h = rem >= 12 ? 1 : 0, m0 = 4 * (rem - 12 * h);
     const f32x4 v = m0 < KH ? *(const f32x4*)(xs + r * MLP2_XS + KH * h + m0) : f32x4{0.f, 0.f, 0.f, 0.f};
+    out |= !(fabsf(v.x) < MLP2_X_LIMIT) | !(fabsf(v.y) < MLP2_X_LIMIT) | !(fabsf(v.z) < MLP2_X_LIMIT) |
+           !(fabsf(v.w) < MLP2_X_LIMIT);
     h4 ch, cl, hh;
     split_d4(v, ch, cl, hh);
     _Float16* d = xf + r * MLP2_FS + 48 * h + m0;
@@ -193,6 +240,7 @@ __device__ __forceinline__ void presplit_tile(const float* xs, _Float16* xf, _Fl
     *(h4*)(d + 96 * MLP2_TS) = cl;
     *(h4*)(d + 192 * MLP2_TS) = hh;
   }
+  return out;
 }
 
 // NWM: launch bound in waves (12: any width <= 384, 168-VGPR budget; 4: F <= 128, 256 budget)
@@ -209,8 +257,12 @@ __device__ __forceinline__ void presplit_tile(const float* xs, _Float16* xf, _Fl
 //   non-finite forward accumulator or dW1 block (an input, dZ1 or weight outside the fp16 range)
 //   sets the guard word; the exact instantiation launched behind this one then recomputes the
 //   step into the same slabs (and exits at once otherwise).
-template <int KH, int ACT1, bool DROP, int NWM, bool SPLIT>
+// CONTIG (12-wave split kernel only): the launch has contiguous rows (no gather index) and P >= 32,
+//   so the gather staging, the index lookup, the P < 32 division of TileImg::of and their
+//   loop-carried state do not exist in the tile loop (stage_contig)
+template <int KH, int ACT1, bool DROP, int NWM, bool SPLIT, bool CONTIG = false>
 __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(NWM == MLP2_MAXW || ACT1 < 0 ? 1 : MLP2_W88, 8))) mlp2_kernel(Args args) {
+  static_assert(!CONTIG || (SPLIT && NWM == MLP2_MAXW), "CONTIG is an instantiation of the pre-split kernel");
   if (!SPLIT && args.guard && __hip_atomic_load(args.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != args.epoch) return;
 #ifdef MLP2_STAMPS
   const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
@@ -223,6 +275,10 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   // buffer is then single (consumed by the split before the barrier that opens its tile)
   constexpr bool PRE = SPLIT && NWM == MLP2_MAXW;
   constexpr int NXB = PRE ? 1 : 2;
+  // LEAN: the pre-split kernel with a compiled-in layer-1 activation (tanh, softsign: act(0) = 0)
+  // carries no per-value selects for its pad columns; the runtime-activation variant keeps them
+  // (sigmoid(0) != 0)
+  constexpr bool LEAN = PRE && ACT1 >= 0;
   // A1 park in the bank-quad slots of a1_row; the 4-wave kernel pays for the padding with 3-float loss
   // accumulators (HS: [NT][3], 128 floats fewer at NT = 128) so it keeps four workgroups per CU — the
   // 12-wave one keeps [NT][4] (3-float rows there push its tile loop over the VGPR budget)
@@ -239,11 +295,15 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   const int NT = blockDim.x;
   const int n = wave * 32 + l32;
   const bool nok = n < F;
-  // LDS: X tiles [2][32][MLP2_XS] | labels [2][128] | head partials [NCB][T][4] | dZ2 [T][4] | scratch
+  // LDS: X tiles [2][32][MLP2_XS] | labels [2][128] | head partials [NPR][T][4] | dZ2 [T][4] | scratch
+  // (geom).  The 12-wave kernels keep MLP2_MAXW partial rows, rows [NCB, 12) zeroed once below, so
+  // the head sums twelve unconditional loads (the + 0.f of an absent wave, as before); the 4-wave
+  // kernel's LDS is sized for four workgroups per CU and keeps NCB rows
+  const int NPR = NWM == MLP2_MAXW ? MLP2_MAXW : NCB;
   float* xbuf = lds;
   float* lbuf = xbuf + NXB * MLP2_XF;
   float* part = lbuf + 2 * MLP2_LAB;
-  float* dz2 = part + NCB * T * 4;
+  float* dz2 = part + NPR * T * 4;
   float* a1s = dz2 + T * 4;       // [NCB][MLP2_A1W]: layer-1 activations, forward -> backward (a1_row)
   float* w2t = a1s + NCB * A1S;  // [NCB * 32][4]: W2 rows (zero past F), then b2 [4]
   float* b2t = w2t + NCB * 128;
@@ -273,7 +333,15 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   // one memory round trip instead of eight serial ones (W1 in two halves, W2[n], b1, the W2 table
   // twice, b2, the tile: ~16 k cycles, the largest phase of a one-tile launch, P = 1 per-step fit).
   // The DMA goes first: hipcc's vmcnt waits count only its own (younger) loads, so they stay exact.
-  if (blockIdx.x < ntiles) stage_tile(args, xbuf, lbuf, (int64_t)blockIdx.x * T, ti, wave, NCB, lane, Cin, labels);
+  // CONTIG: the next tile to stage, advanced by one grid stride of rows per tile (unused, and so
+  // not computed, in the other instantiations)
+  const float* xnext = CONTIG ? args.x + (int64_t)blockIdx.x * T * Cin : nullptr;
+  const int64_t xstep = CONTIG ? (int64_t)gridDim.x * T * Cin : 0;
+  if (blockIdx.x < ntiles) {
+    if constexpr (CONTIG) stage_contig(args, xbuf, lbuf, xnext, (int64_t)blockIdx.x * T, ti, wave, NCB, Cin, labels);
+    else stage_tile(args, xbuf, lbuf, (int64_t)blockIdx.x * T, ti, wave, NCB, lane, Cin, labels);
+  }
+  xnext += xstep;
   const int nc = min(n, F - 1);
   const float w2a = W2[nc * 3], w2b = W2[nc * 3 + 1], w2c = W2[nc * 3 + 2];
   const int o_bias = __builtin_amdgcn_readfirstlane(o[O_BIAS]), o_aux1 = __builtin_amdgcn_readfirstlane(o[O_AUX1]);
@@ -294,6 +362,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   // dZ1 column n enters the dW1 MFMAs scaled by s2 (from max_j |W2[n][j]|, its only per-column
   // factor: s2 max |W2[n]| in [2^2, 2^3)), dW1 leaves as acc / (C s2)
   float inv1 = 1.f, s2 = 1.f;
+  bool wbad = false;  // PRE: a W1 fragment of this lane's column is not finite (the weight side of the guard)
   if constexpr (SPLIT) {
     f32x8 v[6];
 #pragma unroll
@@ -321,7 +390,18 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     const float s1 = pow2_scale(mx, 13);
     inv1 = SPLIT_INV_C / s1;
 #pragma unroll
-    for (int s = 0; s < 6; ++s) wsp[s] = split_w8(v[s] * s1);
+    for (int s = 0; s < 6; ++s) {
+      const f32x8 vs = v[s] * s1;
+      wsp[s] = split_w8(vs);
+      // the scaled value, per value (fmaxf drops a NaN from mx): its hi half fp16(w s1) is infinite
+      // from 65520 on — an infinite or NaN entry (s1 = 1), or a finite column maximum from about
+      // 2^102 on, past pow2_scale's exponent clamp (s1 stays at 2^-86); below that every fragment
+      // is finite (|lo| <= 2^10 x half an fp16 ulp)
+      if (PRE) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wbad |= !(fabsf(vs[j]) < 65520.f);
+      }
+    }
     s2 = pow2_scale(nok ? fmaxf(fmaxf(fabsf(w2a), fabsf(w2b)), fabsf(w2c)) : 0.f, 2);
   } else {
 #pragma unroll
@@ -331,7 +411,12 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       wreg[m] = (k < Cin && nok) ? wv : 0.f;
     }
   }
-  bool bad = false;
+  // PRE: the forward side of the overflow guard is checked where the values are already in hand and
+  // off the tile loop's critical path — the data by presplit_tile (every tile passes through it once:
+  // prologue, head shadow or the late site), W1 above: a non-finite fragment makes the accumulator
+  // of every tile non-finite (inf x, or 0 x inf = NaN), so it flags the launch as soon as the
+  // workgroup has a tile.  With finite fragments on both sides the fp32 accumulator stays finite
+  bool bad = PRE && wbad && blockIdx.x < ntiles;
   {
     // the per-unit scalars live in LDS across the tile loop, not in 3 loop-carried VGPRs (the
     // 12-wave variant sits at the 168-VGPR budget; in registers they pushed a W1 fragment to scratch)
@@ -363,11 +448,15 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     const int r = i >> 4, c = Cin + (i & 15);
     if (c < 96) xbuf[r * MLP2_XS + c] = 0.f;
   }
+  // the partial rows of the absent waves [NCB, NPR): zero for the whole launch
+  for (int i = NCB * T * 4 + threadIdx.x; i < NPR * T * 4; i += NT) part[i] = 0.f;
   __syncthreads();
   if constexpr (PRE) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar_lds();
-    presplit_tile<KH>(xbuf, xfb, xtb, threadIdx.x, NT);
+    // (a workgroup without a tile splits whatever its LDS holds: not data, so not checked)
+    const bool xbad = presplit_tile<KH>(xbuf, xfb, xtb, threadIdx.x, NT);
+    bad |= xbad && blockIdx.x < ntiles;
   }
   int buf = 0;
 #ifdef MLP2_STAMPS
@@ -379,6 +468,13 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
 #define STAMP(i) do {} while (0)
 #endif
   for (int tile = blockIdx.x; tile < (int)ntiles; tile += gridDim.x, buf ^= 1, ti.advance(dq, dr)) {
+    // PRE: the lane's coordinates recomputed per tile (lane_now: a few VALU ops) — hoisted to kernel
+    // entry they and the LDS addresses derived from them stay live across the whole loop, at the
+    // register budget the price was a W1 fragment in scratch, reloaded per tile behind a vmcnt(0)
+    // that waits for the next tile's LDS-DMA
+    const int tlane = PRE ? lane_now() : lane, thalf = tlane >> 5, tl32 = tlane & 31;
+    const int tcol = wave * 32 + tl32;
+    const bool tok = tcol < F;
     const int64_t row0 = (int64_t)tile * T;
     const float* xs = xbuf + (PRE ? 0 : buf) * MLP2_XF;
     const float* lab = lbuf + buf * MLP2_LAB;
@@ -397,26 +493,40 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     if (tile + gridDim.x < ntiles) {
       TileImg tn = ti;
       tn.advance(dq, dr);
-      stage_tile(args, xbuf + (PRE ? 0 : (buf ^ 1)) * MLP2_XF, lbuf + (buf ^ 1) * MLP2_LAB,
-                 (int64_t)(tile + gridDim.x) * T, tn, wave, NCB, lane, Cin, labels);
+      if constexpr (CONTIG) {
+        stage_contig(args, xbuf, lbuf + (buf ^ 1) * MLP2_LAB, xnext, (int64_t)(tile + gridDim.x) * T, tn,
+                     wave, NCB, Cin, labels);
+        xnext += xstep;
+      } else {
+        stage_tile(args, xbuf + (PRE ? 0 : (buf ^ 1)) * MLP2_XF, lbuf + (buf ^ 1) * MLP2_LAB,
+                   (int64_t)(tile + gridDim.x) * T, tn, wave, NCB, tlane, Cin, labels);
+      }
     }
 
     STAMP(2);
     // ---- forward: Z1 = X.W1 (+b1, act, dropout) and the head partials ----
     uint32_t dmask = 0;  // layer-1 dropout keep bits of this lane's 16 rows (reused by backward)
     {
-      const float* ap = xs + l32 * MLP2_XS + half * KH;
+      const float* ap = xs + tl32 * MLP2_XS + thalf * KH;
       f32x16 acc = {};
       if constexpr (PRE) {
-        const _Float16* fp = xfb + l32 * MLP2_FS + 48 * half;
+        const _Float16* fp = xfb + tl32 * MLP2_FS + 48 * thalf;
+        // two-deep fragment buffer: the three reads of K-step s + 1 are issued before K-step s's
+        // MFMAs, so an MFMA waits for reads a whole K-step old, not for its own fragment's round trip
+        auto frag = [&](int s) {
+          return SplitD{*(const h8*)(fp + 8 * s), *(const h8*)(fp + 32 * MLP2_FS + 8 * s),
+                        *(const h8*)(fp + 64 * MLP2_FS + 8 * s)};
+        };
+        SplitD xd = frag(0);
 #pragma unroll
         for (int s = 0; s < 6; ++s) {
-          const SplitD xd = {*(const h8*)(fp + 8 * s), *(const h8*)(fp + 32 * MLP2_FS + 8 * s),
-                             *(const h8*)(fp + 64 * MLP2_FS + 8 * s)};
-          acc = mfma3_dw(xd, wsp[s], acc);
+          SplitD xn = xd;
+          if (s + 1 < 6) xn = frag(s + 1);
           __builtin_amdgcn_sched_barrier(0);
+          acc = mfma3_dw(xd, wsp[s], acc);
+          xd = xn;
         }
-        bad |= !(fabsf(sum16(acc)) <= 3.0e38f);
+        // (no accumulator check here: presplit_tile and the prologue's W1 check flag the same launches)
         STAMP(3);
       } else if constexpr (SPLIT) {
 #pragma unroll
@@ -440,33 +550,35 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         }
       }
       if (DROP) {
-        if (P >= 32) {  // two images at most: two hashes per lane per tile
-          const bool k0 = drop_hash(args.seed, e1.drop, (uint64_t)(ti.img0 + args.img_off), n) >= e1.thr;
-          const bool k1 = drop_hash(args.seed, e1.drop, (uint64_t)(ti.img0 + 1 + args.img_off), n) >= e1.thr;
+        if (CONTIG || P >= 32) {  // two images at most: two hashes per lane per tile
+          const bool k0 = drop_hash(args.seed, e1.drop, (uint64_t)(ti.img0 + args.img_off), tcol) >= e1.thr;
+          const bool k1 = drop_hash(args.seed, e1.drop, (uint64_t)(ti.img0 + 1 + args.img_off), tcol) >= e1.thr;
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            const int r = (g & 3) + 8 * (g >> 2) + 4 * half;
+            const int r = (g & 3) + 8 * (g >> 2) + 4 * thalf;
             dmask |= (ti.rem0 + r >= P ? k1 : k0) ? (1u << g) : 0u;
           }
         } else {
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            const int r = (g & 3) + 8 * (g >> 2) + 4 * half;
-            dmask |= drop_hash(args.seed, e1.drop, (uint64_t)(ti.of(r) + args.img_off), n) >= e1.thr
+            const int r = (g & 3) + 8 * (g >> 2) + 4 * thalf;
+            dmask |= drop_hash(args.seed, e1.drop, (uint64_t)(ti.of(r) + args.img_off), tcol) >= e1.thr
                          ? (1u << g) : 0u;
           }
         }
       }
-      const f32x4 cs = *(const f32x4*)(colt + n * 4);  // (inv1, b1, s2, -)
+      const f32x4 cs = *(const f32x4*)(colt + tcol * 4);  // (inv1, b1, s2, -)
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
         float z = act1_f<ACT1, SPLIT>(e1.act, SPLIT ? fmaf(acc[g], cs.x, cs.y) : acc[g] + cs.y);
         if (DROP) z = (dmask >> g) & 1u ? z * inv_keep1 : 0.f;
-        acc[g] = nok ? z : 0.f;
+        // LEAN: a pad column (n >= F) has a zero W1 column, b1 = 0 and zero W2 rows, and the
+        // compiled-in activations map 0 to 0: its z is already exactly 0 without a select
+        acc[g] = LEAN || tok ? z : 0.f;
       }
       // park A1 in LDS across the head phase (16 VGPRs fewer live through the loss epilogue)
 #pragma unroll
-      for (int g = 0; g < 16; ++g) a1s[wave * A1S + (PAD1 ? a1_row(g) : 64 * g) + lane] = acc[g];
+      for (int g = 0; g < 16; ++g) a1s[wave * A1S + (PAD1 ? a1_row(g) : 64 * g) + tlane] = acc[g];
       // head partials from the parked A1 (a row-on-lane read of this wave's own LDS region, no
       // cross-lane shuffles): lane (row r = l32, half h) dots A1[r][16 h .. 16 h + 16) with the
       // matching W2 rows, the two halves are combined with one xor-32 exchange
@@ -474,9 +586,9 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       {
-        const int r = l32, hh = (r >> 2) & 1, gr = (r & 3) + 4 * (r >> 3);
-        const float* ar = a1s + wave * A1S + (PAD1 ? a1_row(gr) : 64 * gr) + hh * 32 + 16 * half;
-        const float* wr = w2t + (wave * 32 + 16 * half) * 4;
+        const int r = tl32, hh = (r >> 2) & 1, gr = (r & 3) + 4 * (r >> 3);
+        const float* ar = a1s + wave * A1S + (PAD1 ? a1_row(gr) : 64 * gr) + hh * 32 + 16 * thalf;
+        const float* wr = w2t + (wave * 32 + 16 * thalf) * 4;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; i += 4) {
@@ -492,7 +604,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         s0 += __shfl_xor(s0, 32, 64);
         s1 += __shfl_xor(s1, 32, 64);
         s2 += __shfl_xor(s2, 32, 64);
-        if (half == 0) *(f32x4*)(part + (wave * T + r) * 4) = f32x4{s0, s1, s2, 0.f};
+        if (thalf == 0) *(f32x4*)(part + (wave * T + r) * 4) = f32x4{s0, s1, s2, 0.f};
       }
     }
     STAMP(4);
@@ -504,17 +616,17 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     STAMP(5);
     if constexpr (PRE) {
       if (early && wave >= 2 && tile + gridDim.x < ntiles)
-        presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x - 128, NT - 128);
+        bad |= presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x - 128, NT - 128);
     }
 
     // ---- head: sum partials (fixed wave order) + b2, epilogue, loss / output ----
-    for (int it = threadIdx.x; it < T * 3 && threadIdx.x < NT3; it += NT3) {
+    auto head_item = [&](int it) {
       const int r = it / 3, j = it - r * 3;
       const int64_t R = row0 + r;
       float z = b2t[j];
       float pv[MLP2_MAXW];  // all partial loads in flight, summed in fixed wave order
 #pragma unroll
-      for (int w = 0; w < MLP2_MAXW; ++w) pv[w] = w < NCB ? part[(w * T + r) * 4 + j] : 0.f;
+      for (int w = 0; w < MLP2_MAXW; ++w) pv[w] = NWM == MLP2_MAXW || w < NCB ? part[(w * T + r) * 4 + j] : 0.f;
       // the label and this thread's loss accumulators read with the partials (one LDS round trip;
       // read-modify-written one by one behind the dz2 store they were three more on the head's path)
       float lv = 0.f, ha0 = 0.f, ha1 = 0.f, ha2 = 0.f;
@@ -533,7 +645,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       int64_t img = 0;
       bool k2 = true;
       if (d2) {
-        img = ti.of(r) + args.img_off;
+        img = ti.of<CONTIG>(r) + args.img_off;
         if (ACT1 >= 0) k2 = drop_hash(args.seed, e2.drop, (uint64_t)img, j) >= e2.thr;
       }
       const float p = ACT1 >= 0 ? (d2 ? (k2 ? z / e2.keep : 0.f) : z) : e_fwd(e2, args.seed, img, j, z);
@@ -556,6 +668,12 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         hacc[threadIdx.x * HS + 1] = ha1;
         hacc[threadIdx.x * HS + 2] = ha2;
       }
+    };
+    if constexpr (NWM == MLP2_MAXW) {
+      // at least 320 threads for the 96 items: one item per thread
+      if (threadIdx.x < T * 3) head_item(threadIdx.x);
+    } else {
+      for (int it = threadIdx.x; it < T * 3 && threadIdx.x < NT3; it += NT3) head_item(it);
     }
     STAMP(6);
     if constexpr (PRE) {
@@ -567,7 +685,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       bar_lds();
       STAMP(7);
       if (!early && tile + gridDim.x < ntiles) {
-        presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x, NT);
+        bad |= presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x, NT);
       }
       if (!train) continue;
     } else {
@@ -578,14 +696,21 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     STAMP(8);
     // ---- backward: dA1 = dZ2.W2^T, dZ1, dW2, db1 in registers; dW1 += X^T.dZ1 on MFMA ----
     {
-      const f32x4 w2v = *(const f32x4*)(w2t + n * 4);
-      const float s2 = colt[n * 4 + 2];
+      const f32x4 w2r = *(const f32x4*)(w2t + tcol * 4);
+      const float s2 = colt[tcol * 4 + 2];
+      // PRE: the dW1 operand's power-of-two scale s2 rides on the three W2 values of dA1 (3 multiplies
+      // instead of 16 on dZ1; exact, so dZ1 s2 has the same bits either way) and db1 accumulates
+      // scaled, unscaled once at the flush
+      const f32x4 w2v = PRE ? f32x4{w2r.x * s2, w2r.y * s2, w2r.z * s2, 0.f} : w2r;
       // dZ1 of accumulator register g (row (g & 3) + 8 (g >> 2) + 4 h), dW2 / db1 on the way
       auto dz_of = [&](int g) {
-        const int r = (g & 3) + 8 * (g >> 2) + 4 * half;
+        const int r = (g & 3) + 8 * (g >> 2) + 4 * thalf;
         const f32x4 d = *(const f32x4*)(dz2 + r * 4);
-        const float a = a1s[wave * A1S + (PAD1 ? a1_row(g) : 64 * g) + lane];
-        const float da = d.x * w2v.x + d.y * w2v.y + d.z * w2v.z;
+        const float a = a1s[wave * A1S + (PAD1 ? a1_row(g) : 64 * g) + tlane];
+        // PRE: the fused form this sum compiles to, spelled out — with the scale folded into w2v the
+        // bits stay the same only in that form, in every instantiation
+        const float da = PRE ? fmaf(d.z, w2v.z, fmaf(d.x, w2v.x, d.y * w2v.y))
+                             : d.x * w2v.x + d.y * w2v.y + d.z * w2v.z;
         float gz, av = a;
         if (DROP) {
           gz = (dmask >> g) & 1u ? da * inv_keep1 : 0.f;
@@ -593,21 +718,29 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         } else {
           gz = da;
         }
-        gz = nok ? gz * act1_g<ACT1>(e1.act, av) : 0.f;
+        // LEAN: a pad column's W2 row is zero, so its dA1, and with it dZ1, is already 0 — or NaN under
+        // a non-finite dZ2, which stays inside the pad column: its dW1 / db1 / dW2 are never stored
+        // and the flush keeps it out of the overflow check
+        // (db1 sums the rounded dZ1 the MFMAs see: without the select between them the product and
+        // the sum would contract to one fma)
+        {
+#pragma clang fp contract(off)
+          gz = LEAN || tok ? gz * act1_g<ACT1>(e1.act, av) : 0.f;
+          db1 += gz;
+        }
         dw2[0] = fmaf(a, d.x, dw2[0]);
         dw2[1] = fmaf(a, d.y, dw2[1]);
         dw2[2] = fmaf(a, d.z, dw2[2]);
-        db1 += gz;
         return gz;
       };
       if constexpr (PRE) {
         // dZ1 of K-step 0 -> split -> its 9 MFMAs, with the VALU of K-step 1's dZ1 free to issue
         // under them (no scheduling fences between the two), then K-step 1's MFMAs
-        const _Float16* th = xtb + buf * 3 * 96 * MLP2_TS + l32 * MLP2_TS + 8 * half;
+        const _Float16* th = xtb + buf * 3 * 96 * MLP2_TS + tl32 * MLP2_TS + 8 * thalf;
         f32x8 dv0, dv1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv0[j] = dz_of(j);
-        const SplitW d0 = split_w8(dv0 * s2);
+        const SplitW d0 = split_w8(dv0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
@@ -617,7 +750,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv1[j] = dz_of(8 + j);
         __builtin_amdgcn_sched_barrier(0);
-        const SplitW d1 = split_w8(dv1 * s2);
+        const SplitW d1 = split_w8(dv1);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
           const _Float16* q = th + 16 + kb * 32 * MLP2_TS;
@@ -637,7 +770,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
           const SplitW dsp = split_w8(dv * s2);
 #pragma unroll
           for (int kb = 0; kb < NKB; ++kb) {
-            const float* xp = xs + (4 * half) * MLP2_XS + kb * 32 + l32;
+            const float* xp = xs + (4 * thalf) * MLP2_XS + kb * 32 + tl32;
             f32x8 xv;
 #pragma unroll
             for (int j = 0; j < 8; ++j) xv[j] = xp[(16 * s + 8 * (j >> 2) + (j & 3)) * MLP2_XS];
@@ -655,7 +788,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
           // X^T block: lane reads X[r(g)][k = 32 kb + l32]
-          const float* xp = xs + (4 * half) * MLP2_XS + kb * 32 + l32;
+          const float* xp = xs + (4 * thalf) * MLP2_XS + kb * 32 + tl32;
           f32x16 acc = dw[kb];
           auto xat = [&](int g) { return xp[((g & 3) + 8 * (g >> 2)) * MLP2_XS]; };
           float x0 = xat(0), x1 = xat(1);
@@ -680,6 +813,10 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     printf("STAMP w%d bwd+tail %u bar1 %u stage %u fwdmfma %u act+part %u bar2 %u head %u bar3 %u presplit %u\n", wave,
            ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7], ph[8]);
 #endif
+  // (the lane's coordinates again: not kept live across the tile loop in the pre-split kernels)
+  const int flane = PRE ? lane_now() : lane, fhalf = flane >> 5;
+  const int fcol = wave * 32 + (flane & 31);
+  const bool fok = fcol < F;
   if (mode == MODE_FWD) {
     if (SPLIT && bad) __hip_atomic_store(args.guard, args.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
@@ -694,7 +831,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   const int oW = __builtin_amdgcn_readfirstlane(o[O_W]), oB = __builtin_amdgcn_readfirstlane(o[O_BIAS]);
   const int oA0 = __builtin_amdgcn_readfirstlane(o[O_AUX0]), oA1 = __builtin_amdgcn_readfirstlane(o[O_AUX1]);
   __syncthreads();
-  const float s2f = colt[n * 4 + 2];
+  const float s2f = colt[fcol * 4 + 2];
   if (train) {
     const float scw = SPLIT ? sc * (SPLIT_INV_C / s2f) : sc;
     float chk = 0.f;
@@ -703,19 +840,22 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       if (SPLIT) chk += sum16(dw[kb]);
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int k = kb * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
-        if (k < Cin && nok) ws[oW + (size_t)k * F + n] = dw[kb][g] * scw;
+        const int k = kb * 32 + (g & 3) + 8 * (g >> 2) + 4 * fhalf;
+        if (k < Cin && fok) ws[oW + (size_t)k * F + fcol] = dw[kb][g] * scw;
       }
     }
-    if (SPLIT) bad |= !(fabsf(chk) <= 3.0e38f);
-    const float tb = db1 + __shfl_xor(db1, 32, 64);
+    // (a LEAN pad column's accumulators are zero, or hold the NaN of a non-finite dZ2 that the
+    // select-free dZ1 lets through: never stored, and not part of the check)
+    if (SPLIT) bad |= (!LEAN || fok) && !(fabsf(chk) <= 3.0e38f);
+    // PRE: db1 was accumulated at the dW1 operand's scale s2 (a power of two: exact to undo)
+    const float tb = (db1 + __shfl_xor(db1, 32, 64)) * (PRE ? 1.f / s2f : 1.f);
     float t2[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) t2[j] = dw2[j] + __shfl_xor(dw2[j], 32, 64);
-    if (half == 0 && nok) {
-      if (oB >= 0) ws[oB + n] = tb * sc;
+    if (fhalf == 0 && fok) {
+      if (oB >= 0) ws[oB + fcol] = tb * sc;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) ws[oA0 + n * 3 + j] = t2[j] * sc;
+      for (int j = 0; j < 3; ++j) ws[oA0 + fcol * 3 + j] = t2[j] * sc;
     }
 #ifdef MLP2_STAMPS
     rtA = __builtin_amdgcn_s_memrealtime();
@@ -726,9 +866,9 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     if (oA1 >= 0) {
       for (int j = wave; j < 3; j += NT >> 6) {
         float s = 0.f;
-        for (int i = j + 3 * lane; i < NT3; i += 192) s += hacc[i * HS + 2];
+        for (int i = j + 3 * flane; i < NT3; i += 192) s += hacc[i * HS + 2];
         s = wave_sum(s);
-        if (lane == 0) ws[oA1 + j] = s * sc;
+        if (flane == 0) ws[oA1 + j] = s * sc;
       }
     }
 #ifdef MLP2_STAMPS
@@ -741,7 +881,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
 #endif
   if (SPLIT && bad) __hip_atomic_store(args.guard, args.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const float a = wave_sum(hacc[threadIdx.x * HS + 0]), b = wave_sum(hacc[threadIdx.x * HS + 1]);
-  if (lane == 0) { red[wave] = a; red[MLP2_MAXW + wave] = b; }
+  if (flane == 0) { red[wave] = a; red[MLP2_MAXW + wave] = b; }
   __syncthreads();
   if (threadIdx.x == 0) {
     float s0 = 0.f, s1 = 0.f;
@@ -1144,31 +1284,36 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 // ---- host-side dispatch ---------------------------------------------------------------------
 typedef void (*mlp2_fn)(Args);
 
-template <int KH, bool DROP, int NWM, bool SPLIT>
+template <int KH, bool DROP, int NWM, bool SPLIT, bool CONTIG = false>
 static mlp2_fn pick_act(int act, int act2) {
-  if (act2 != ACT_LINEAR) return mlp2_kernel<KH, -1, DROP, NWM, SPLIT>;
-  if (act == ACT_TANH) return mlp2_kernel<KH, ACT_TANH, DROP, NWM, SPLIT>;
-  if (act == ACT_SOFTSIGN) return mlp2_kernel<KH, ACT_SOFTSIGN, DROP, NWM, SPLIT>;
-  return mlp2_kernel<KH, -1, DROP, NWM, SPLIT>;
+  if (act2 != ACT_LINEAR) return mlp2_kernel<KH, -1, DROP, NWM, SPLIT, CONTIG>;
+  if (act == ACT_TANH) return mlp2_kernel<KH, ACT_TANH, DROP, NWM, SPLIT, CONTIG>;
+  if (act == ACT_SOFTSIGN) return mlp2_kernel<KH, ACT_SOFTSIGN, DROP, NWM, SPLIT, CONTIG>;
+  return mlp2_kernel<KH, -1, DROP, NWM, SPLIT, CONTIG>;
 }
 
+// contig: the contiguous-rows instantiation of the 12-wave split kernel (ignored by the others)
 template <bool DROP, bool SPLIT>
-static mlp2_fn pick_d(int kh, int act, int act2, int ncb) {
+static mlp2_fn pick_d(int kh, int act, int act2, int ncb, bool contig) {
   if (ncb <= 4) {
     if (kh == 44) return pick_act<44, DROP, 4, SPLIT>(act, act2);  // 88-channel BlazeFace tap (Model-88)
     if (kh == 48) return pick_act<48, DROP, 4, SPLIT>(act, act2);  // 96-channel tap (Model-96)
+  }
+  if constexpr (SPLIT) {
+    if (contig && kh == 44) return pick_act<44, DROP, MLP2_MAXW, SPLIT, true>(act, act2);
+    if (contig && kh == 48) return pick_act<48, DROP, MLP2_MAXW, SPLIT, true>(act, act2);
   }
   if (kh == 44) return pick_act<44, DROP, MLP2_MAXW, SPLIT>(act, act2);
   if (kh == 48) return pick_act<48, DROP, MLP2_MAXW, SPLIT>(act, act2);
   return nullptr;
 }
 
-static mlp2_fn pick(const int* w, bool split = false) {
+static mlp2_fn pick(const int* w, bool split = false, bool contig = false) {
   const int* o = w + w[H_OPS_OFF];
   const int kh = ((o[O_K] + 7) & ~7) / 2, act = o[O_EACT], act2 = o[O_AUX2];
   if (split)
-    return o[O_EDROP] >= 0 ? pick_d<true, true>(kh, act, act2, o[O_MODE]) : pick_d<false, true>(kh, act, act2, o[O_MODE]);
-  return o[O_EDROP] >= 0 ? pick_d<true, false>(kh, act, act2, o[O_MODE]) : pick_d<false, false>(kh, act, act2, o[O_MODE]);
+    return o[O_EDROP] >= 0 ? pick_d<true, true>(kh, act, act2, o[O_MODE], contig) : pick_d<false, true>(kh, act, act2, o[O_MODE], contig);
+  return o[O_EDROP] >= 0 ? pick_d<true, false>(kh, act, act2, o[O_MODE], false) : pick_d<false, false>(kh, act, act2, o[O_MODE], false);
 }
 
 static void geom(const int* w, int& kh, int& rbw, int& ncb, int& lds_bytes, int& act, int& drop) {
@@ -1181,7 +1326,8 @@ static void geom(const int* w, int& kh, int& rbw, int& ncb, int& lds_bytes, int&
   rbw = o[O_FLAGS];
   ncb = o[O_MODE];
   const int T = 32;
-  const int rest = 2 * MLP2_LAB + ncb * T * 4 + T * 4 + ncb * MLP2_A1W + ncb * 128 + 4 + ncb * 64 * (ncb > 4 ? 4 : 3) + MLP2_RED + ncb * 128;
+  const int npr = ncb > 4 ? MLP2_MAXW : ncb;  // head partial rows (the 12-wave kernels keep all twelve)
+  const int rest = 2 * MLP2_LAB + npr * T * 4 + T * 4 + ncb * MLP2_A1W + ncb * 128 + 4 + ncb * 64 * (ncb > 4 ? 4 : 3) + MLP2_RED + ncb * 128;
   lds_bytes = (2 * MLP2_XF + rest) * 4;
   // the 12-wave variant's split kernel (PRE): one raw tile buffer + the pre-split halves
   const int pre = (MLP2_XF + rest) * 4 + MLP2_PRE_HALVES * 2;
@@ -1247,7 +1393,9 @@ static int launch_pair(const int* w, const Args& a, int grid, hipStream_t s) {
   }
   const mlp2_fn kr = pick_r(w);
   const int tv = hpe_tev_begin(s);
-  const int rc = kr ? launch_k(kr, 1, MLP2R_LDS_FLOATS * 4, a, grid, s) : launch_k(pick(w, true), ncb, lds_split(w), a, grid, s);
+  // contiguous rows, at most two images per tile: the 12-wave split kernel's CONTIG instantiation
+  const bool contig = a.idx == nullptr && a.P >= 32;
+  const int rc = kr ? launch_k(kr, 1, MLP2R_LDS_FLOATS * 4, a, grid, s) : launch_k(pick(w, true, contig), ncb, lds_split(w), a, grid, s);
   hpe_tev_end(s, tv);
   if (rc) return rc;
   if (split_only()) return 0;
@@ -1270,15 +1418,21 @@ static int per_cu_of(mlp2_fn k, int ncb, int lds) {
   return per_cu < 1 ? 1 : per_cu;
 }
 
-// resident workgroups per CU of this object's kernels for program w: the smaller of the split and
-// exact instantiations
+// resident workgroups per CU of this object's kernels for program w: the smallest of the exact, the
+// split (general and contiguous-rows) and the row-parallel instantiations
 static int cap_per_cu(const int* w) {
   int kh, rbw, ncb, lds, act, drop;
   geom(w, kh, rbw, ncb, lds, act, drop);
-  const int a = per_cu_of(pick(w), ncb, lds), b = per_cu_of(pick(w, true), ncb, lds_split(w));
+  int cap = per_cu_of(pick(w), ncb, lds);
+  const int b = per_cu_of(pick(w, true), ncb, lds_split(w)), bc = per_cu_of(pick(w, true, true), ncb, lds_split(w));
+  cap = b < cap ? b : cap;
+  cap = bc < cap ? bc : cap;
   const mlp2_fn kr = pick_r(w);
-  const int c = kr ? per_cu_of(kr, 1, MLP2R_LDS_FLOATS * 4) : b;
-  return a < b ? (a < c ? a : c) : (b < c ? b : c);
+  if (kr) {
+    const int c = per_cu_of(kr, 1, MLP2R_LDS_FLOATS * 4);
+    cap = c < cap ? c : cap;
+  }
+  return cap;
 }
 }  // namespace MLP2_NS
 
