@@ -48,10 +48,10 @@ namespace MLP2_NS {
 #define MLP2_RED 32             // floats of the end-of-launch loss reduction (2 x MLP2_MAXW, rounded up)
 // pre-split X tiles (SPLIT kernels of the 12-wave variant, see presplit_tile): the three fp16
 // fragments of the data side of split_d8 (hpe_common.h): ch = fp16(C x), cl = fp16(C x - ch), h = fp16(x)
-#define MLP2_FS 104             // row stride (halves) of the forward layout [32 rows][2 x 48]: conflict-free b128
-#define MLP2_TS 40              // row stride (halves) of the transposed layout [96 channels][32 rows]
+#define MLP2_FS 104             // row stride (halves) of the fp16 image [32 rows][2 x 48]: conflict-free b128
+#define MLP2_IMG (3 * 32 * MLP2_FS)  // halves of one tile's image: fragments ch, cl, h
 #define MLP2_A1W (15 * 68 + 64)  // floats of a wave's A1 park (a1_row)
-#define MLP2_PRE_HALVES (3 * 32 * MLP2_FS + 2 * 3 * 96 * MLP2_TS)  // fwd ch, cl, h + 2 parities x transposed ch, cl, h
+#define MLP2_PRE_HALVES (2 * MLP2_IMG)  // two parities: tile t + 1 is split while tile t's backward reads its own
 
 struct E2 {
   int act, drop;
@@ -182,21 +182,34 @@ __device__ __forceinline__ void stage_contig(const Args& args, float* xs, float*
 
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
+typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+
 // One split of the landed X tile per workgroup instead of one per wave (the 12 waves all read the
-// whole tile, in two layouts): every thread turns 4 floats into the three data-side fp16 fragments
-// (ch, cl, h of split_d8), written
-//   * forward layout  xf[r][48 h + m] = X[r][KH h + m] (zero for m >= KH): lane (row r, half h)
-//     reads K-step s as one b128 per fragment at 48 h + 8 s; fragment f at xf + f * 32 * FS;
-//   * transposed      xt[k][p(r)] = X[r][k], p(r) = r with bits 2 and 3 swapped, so the 8 rows
-//     16 s + 8 (j >> 2) + 4 h + (j & 3) of the dW1 K-step s are the contiguous p = 16 s + 8 h + j:
-//     one b128 per (K-step, 32-channel block, fragment) instead of 8 strided b32 reads + a split per
-//     wave; fragment f at xt + f * 96 * TS.
-// Pad channels [C_in, 96) of the raw tile hold zeros, so their xt rows are zero.
-__device__ __forceinline__ void split_d4(f32x4 v, h4& ch, h4& cl, h4& h) {
-  const f32x4 s = v * SPLIT_C;
-  ch = __builtin_convertvector(s, h4);
-  cl = __builtin_convertvector(s - __builtin_convertvector(ch, f32x4), h4);
-  h = __builtin_convertvector(v, h4);
+// whole tile, by rows and by columns): every thread turns 8 floats into the three data-side fp16
+// fragments (ch, cl, h of split_d8), written into ONE image
+//   xf[r][48 h + m] = X[r][KH h + m] (zero for m >= KH), fragment f at xf + f * 32 * FS,
+// that both GEMMs read:
+//   * forward: lane (row r, half h) reads K-step s as one b128 per fragment at 48 h + 8 s;
+//   * dW1 (A = X^T): ds_read_b64_tr_b16 (tr_read8), which hands each lane one channel's values of
+//     four rows — no second, transposed image and no second split of the tile.
+// img_pos is the position of channel c in a row: at KH = 44 the second half starts at position 48
+// (16-byte aligned), so channels >= 44 sit 4 further on; positions [KH, 48) of both halves hold zeros,
+// and the pad channels [C_in, 96) of the raw tile hold zeros.  A 4-channel chunk never straddles the
+// gap; the chunks wholly past the image (channels 92..95 at KH = 44) map to the zeros at 92..95.
+template <int KH>
+__device__ __forceinline__ int img_pos(int c) {
+  if (KH == 48) return c;
+  return c < KH ? c : min(c + 48 - KH, 92);
+}
+// dW1's A operand of one (K-step, 32-channel block, fragment): rows R0 .. R0 + 3 and R0 + 8 .. R0 + 11
+// of the block's 32 channels, delivered channel-on-lane (lane 16 g + i of a half: channel 16 g + i;
+// element j: row R0 + 8 (j >> 2) + (j & 3)).  p is the lane's address: lane 16 g + 4 q + p' supplies
+// (row R0 + q, channels 16 g + 4 p' .. + 3), 8-byte aligned.  EXEC must be all ones here.
+__device__ __forceinline__ h8 tr_read8(const _Float16* p) {
+  typedef __attribute__((address_space(3))) fp16x4* lp;
+  const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp)(p));
+  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp)(p + 8 * MLP2_FS));
+  return __builtin_shufflevector(__builtin_bit_cast(h4, a), __builtin_bit_cast(h4, b), 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // A1 park of a wave: accumulator register g's 64 lanes at row a1_row(g), 68 floats per row slot, so
 // slot t starts on bank quad t; register g takes slot g ^ ((g >> 1) & 4) (rows 8..11 on quads 12..15,
@@ -214,31 +227,22 @@ __device__ __forceinline__ constexpr int a1_row(int g) { return 68 * (g ^ ((g >>
 // NaN, reaches every column's accumulator of its row (0 x inf = NaN), the zero pad columns' too.
 #define MLP2_X_LIMIT (65520.f / SPLIT_C)
 template <int KH>
-__device__ __forceinline__ bool presplit_tile(const float* xs, _Float16* xf, _Float16* xt, int tid, int NT) {
+__device__ __forceinline__ bool presplit_tile(const float* xs, _Float16* xf, int tid, int NT) {
   bool out = false;
-  for (int i = tid; i < 32 * 24; i += NT) {
-    const int r = i / 24, rem = i - r * 24, h = rem >= 12 ? 1 : 0, m0 = 4 * (rem - 12 * h);
-    const f32x4 v = m0 < KH ? *(const f32x4*)(xs + r * MLP2_XS + KH * h + m0) : f32x4{0.f, 0.f, 0.f, 0.f};
-    out |= !(fabsf(v.x) < MLP2_X_LIMIT) | !(fabsf(v.y) < MLP2_X_LIMIT) | !(fabsf(v.z) < MLP2_X_LIMIT) |
-           !(fabsf(v.w) < MLP2_X_LIMIT);
-    h4 ch, cl, hh;
-    split_d4(v, ch, cl, hh);
+  // one 16-byte chunk of the image (8 floats of one row and half) per item: 384 items
+  for (int i = tid; i < 32 * 12; i += NT) {
+    const int r = i / 12, rem = i - r * 12, h = rem >= 6 ? 1 : 0, m0 = 8 * (rem - 6 * h);
+    const float* s = xs + r * MLP2_XS + KH * h + m0;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 a = *(const f32x4*)(s), b = m0 + 4 < KH ? *(const f32x4*)(s + 4) : z;
+    const f32x8 v = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out |= !(fabsf(v[j]) < MLP2_X_LIMIT);
+    const SplitD d8 = split_d8(v);
     _Float16* d = xf + r * MLP2_FS + 48 * h + m0;
-    *(h4*)(d) = ch;
-    *(h4*)(d + 32 * MLP2_FS) = cl;
-    *(h4*)(d + 64 * MLP2_FS) = hh;
-  }
-  for (int i = tid; i < 96 * 8; i += NT) {
-    const int rg = i / 96, k = i - rg * 96, r = 4 * rg;
-    const f32x4 v = {xs[r * MLP2_XS + k], xs[(r + 1) * MLP2_XS + k], xs[(r + 2) * MLP2_XS + k],
-                     xs[(r + 3) * MLP2_XS + k]};
-    const int p = (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1);
-    h4 ch, cl, hh;
-    split_d4(v, ch, cl, hh);
-    _Float16* d = xt + k * MLP2_TS + p;
-    *(h4*)(d) = ch;
-    *(h4*)(d + 96 * MLP2_TS) = cl;
-    *(h4*)(d + 192 * MLP2_TS) = hh;
+    *(h8*)(d) = d8.ch;
+    *(h8*)(d + 32 * MLP2_FS) = d8.cl;
+    *(h8*)(d + 64 * MLP2_FS) = d8.h;
   }
   return out;
 }
@@ -310,8 +314,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   float* hacc = b2t + 4;          // [NT][HS]: per-thread loss / db2 accumulators (sse, sae, db2)
   float* red = hacc + NCB * 64 * HS;  // [2 * MLP2_MAXW]: block reduction of the loss sums
   float* colt = red + MLP2_RED;   // [NCB * 32][4]: per hidden unit (inv1, b1, s2, -), re-read per tile
-  _Float16* xfb = (_Float16*)(colt + NCB * 128);  // PRE: [3][32][MLP2_FS] ch, cl, h; [2][3][96][MLP2_TS]
-  _Float16* xtb = xfb + 3 * 32 * MLP2_FS;
+  _Float16* xfb = (_Float16*)(colt + NCB * 128);  // PRE: [2 parities][3][32][MLP2_FS] ch, cl, h
 
   E2 e1 = {o[O_EACT], o[O_EDROP], (uint32_t)o[O_ETHR], __int_as_float(o[O_EKEEP])};
   E2 e2 = {o[O_AUX2], o[O_TBASE], (uint32_t)o[O_TCOUNT], __int_as_float(o[O_F0])};
@@ -413,7 +416,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   }
   // PRE: the forward side of the overflow guard is checked where the values are already in hand and
   // off the tile loop's critical path — the data by presplit_tile (every tile passes through it once:
-  // prologue, head shadow or the late site), W1 above: a non-finite fragment makes the accumulator
+  // prologue or head shadow), W1 above: a non-finite fragment makes the accumulator
   // of every tile non-finite (inf x, or 0 x inf = NaN), so it flags the launch as soon as the
   // workgroup has a tile.  With finite fragments on both sides the fp32 accumulator stays finite
   bool bad = PRE && wbad && blockIdx.x < ntiles;
@@ -455,7 +458,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar_lds();
     // (a workgroup without a tile splits whatever its LDS holds: not data, so not checked)
-    const bool xbad = presplit_tile<KH>(xbuf, xfb, xtb, threadIdx.x, NT);
+    const bool xbad = presplit_tile<KH>(xbuf, xfb, threadIdx.x, NT);
     bad |= xbad && blockIdx.x < ntiles;
   }
   int buf = 0;
@@ -483,12 +486,17 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     // split before this barrier, the raw buffer is free)
     if constexpr (!PRE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     STAMP(0);
-    // PRE with the head-shadow pre-split (NCB >= 4): every LDS hazard this barrier guards is already
-    // ordered by the previous tile's third barrier — the raw tile was split (and the next raw tile's
-    // landing waited for) before it, xf / the partials / this parity's labels were last read before
-    // it, the A1 park and the loss accumulators are per wave / per thread — so after the first tile
+    // PRE: every LDS hazard this barrier guards is already ordered by the previous tile's two
+    // barriers (the one before the head, B2, and the one after it, B3) — the raw tile was split (and
+    // the next raw tile's landing waited for) before B3, the partials / this parity's labels were last
+    // read before it, the A1 park and the loss accumulators are per wave / per thread.  The fp16 image
+    // has two parities: tile t's forward (before B2(t)) and backward (after B3(t)) read parity p; tile
+    // t + 1 is split into parity p ^ 1 between B2(t) and B3(t), after that parity's last reader (tile
+    // t - 1's backward, which every wave left before B2(t)) and before its next (tile t + 1's forward,
+    // after B3(t)); the writer of parity p for tile t + 2 runs after B2(t + 1), which every wave
+    // reaches only past tile t's backward, the last reader of parity p.  So after the first tile
     // (whose pre-split is ordered only by this barrier) the tile loop runs on two barriers
-    if (!(MLP2_BAR1_SKIP && PRE && NCB >= 4 && tile != (int)blockIdx.x)) bar_lds();
+    if (!(MLP2_BAR1_SKIP && PRE && tile != (int)blockIdx.x)) bar_lds();
     STAMP(1);
     if (tile + gridDim.x < ntiles) {
       TileImg tn = ti;
@@ -510,7 +518,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       const float* ap = xs + tl32 * MLP2_XS + thalf * KH;
       f32x16 acc = {};
       if constexpr (PRE) {
-        const _Float16* fp = xfb + tl32 * MLP2_FS + 48 * thalf;
+        const _Float16* fp = xfb + buf * MLP2_IMG + tl32 * MLP2_FS + 48 * thalf;
         // two-deep fragment buffer: the three reads of K-step s + 1 are issued before K-step s's
         // MFMAs, so an MFMA waits for reads a whole K-step old, not for its own fragment's round trip
         auto frag = [&](int s) {
@@ -608,15 +616,15 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       }
     }
     STAMP(4);
-    // PRE with >= 4 waves: the next tile's pre-split runs on waves 2.. during the head (waves 0-1),
-    // so its pieces must have landed by this barrier instead of the next one
-    const bool early = PRE && NCB >= 4;
-    if (early) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // PRE (NCB >= 5: pick_d sends narrower layers to the 4-wave kernel): the next tile's pre-split
+    // runs on waves 2.. during the head (waves 0-1), into the image's other parity, so its pieces
+    // must have landed by this barrier instead of the next one
+    if constexpr (PRE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar_lds();
     STAMP(5);
     if constexpr (PRE) {
-      if (early && wave >= 2 && tile + gridDim.x < ntiles)
-        bad |= presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x - 128, NT - 128);
+      if (wave >= 2 && tile + gridDim.x < ntiles)
+        bad |= presplit_tile<KH>(xbuf, xfb + (buf ^ 1) * MLP2_IMG, threadIdx.x - 128, NT - 128);
     }
 
     // ---- head: sum partials (fixed wave order) + b2, epilogue, loss / output ----
@@ -677,16 +685,11 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     }
     STAMP(6);
     if constexpr (PRE) {
-      // the next tile landed -> barrier -> split it (forward layout: this tile's forward is done;
-      // transposed: the other parity, this tile's backward reads its own), unless waves 2.. split
-      // it during the head above (`early`: round 2 measured that slower, 3.80 -> 3.92 ms; on the
-      // round-5 kernel it is faster, 3.235 -> 3.128 ms on configs[3], A/B x3)
+      // the head is done and the next tile is split (by waves 2.. during the head: splitting it here,
+      // after the barrier, measured slower, 3.235 -> 3.128 ms on configs[3], A/B x3)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       bar_lds();
       STAMP(7);
-      if (!early && tile + gridDim.x < ntiles) {
-        bad |= presplit_tile<KH>(xbuf, xfb, xtb + (buf ^ 1) * 3 * 96 * MLP2_TS, threadIdx.x, NT);
-      }
       if (!train) continue;
     } else {
       if (!train) continue;  // the next tile's first barrier orders part / lab reuse
@@ -736,26 +739,34 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       if constexpr (PRE) {
         // dZ1 of K-step 0 -> split -> its 9 MFMAs, with the VALU of K-step 1's dZ1 free to issue
         // under them (no scheduling fences between the two), then K-step 1's MFMAs
-        const _Float16* th = xtb + buf * 3 * 96 * MLP2_TS + tl32 * MLP2_TS + 8 * thalf;
+        // The A operand X^T by transposed reads of this tile's image (tr_read8): K-step s, lane half
+        // h, element j <-> tile row 16 s + 8 (j >> 2) + 4 h + (j & 3), so R0 = 16 s + 4 h; lane
+        // 16 g + 4 q + p of the half addresses row R0 + q, channels 32 kb + 16 g + 4 p .. + 3.  One lane
+        // term recomputed per tile; K-step, block (at KH = 48) and fragment are immediate offsets
+        const int tc = (tl32 & 16) + 4 * (tl32 & 3);
+        const _Float16* th = xfb + buf * MLP2_IMG + (4 * thalf + ((tl32 >> 2) & 3)) * MLP2_FS;
+        auto xt_of = [&](int s, int kb) {
+          const _Float16* q = th + 16 * s * MLP2_FS + img_pos<KH>(32 * kb + tc);
+          return SplitD{tr_read8(q), tr_read8(q + 32 * MLP2_FS), tr_read8(q + 64 * MLP2_FS)};
+        };
         f32x8 dv0, dv1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv0[j] = dz_of(j);
         const SplitW d0 = split_w8(dv0);
         __builtin_amdgcn_sched_barrier(0);
+        // (the fence after block 0 keeps the 18 reads of this K-step from all being in flight at once:
+        // without it their 36 VGPRs push a W1 fragment to scratch, reloaded per tile in the forward)
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
-          const _Float16* q = th + kb * 32 * MLP2_TS;
-          dw[kb] = mfma3_dw(SplitD{*(const h8*)(q), *(const h8*)(q + 96 * MLP2_TS), *(const h8*)(q + 192 * MLP2_TS)}, d0, dw[kb]);
+          dw[kb] = mfma3_dw(xt_of(0, kb), d0, dw[kb]);
+          if (kb == 0) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv1[j] = dz_of(8 + j);
         __builtin_amdgcn_sched_barrier(0);
         const SplitW d1 = split_w8(dv1);
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-          const _Float16* q = th + 16 + kb * 32 * MLP2_TS;
-          dw[kb] = mfma3_dw(SplitD{*(const h8*)(q), *(const h8*)(q + 96 * MLP2_TS), *(const h8*)(q + 192 * MLP2_TS)}, d1, dw[kb]);
-        }
+        for (int kb = 0; kb < NKB; ++kb) dw[kb] = mfma3_dw(xt_of(1, kb), d1, dw[kb]);
       } else if constexpr (SPLIT) {
         // K-step s (rows 16 s + 8 (j >> 2) + 4 h + (j & 3)): dZ1 registers 8 s .. 8 s + 7 as the B
         // operand, the matching X^T rows as A; one K-step at a time keeps the live set small
@@ -1329,7 +1340,7 @@ static void geom(const int* w, int& kh, int& rbw, int& ncb, int& lds_bytes, int&
   const int npr = ncb > 4 ? MLP2_MAXW : ncb;  // head partial rows (the 12-wave kernels keep all twelve)
   const int rest = 2 * MLP2_LAB + npr * T * 4 + T * 4 + ncb * MLP2_A1W + ncb * 128 + 4 + ncb * 64 * (ncb > 4 ? 4 : 3) + MLP2_RED + ncb * 128;
   lds_bytes = (2 * MLP2_XF + rest) * 4;
-  // the 12-wave variant's split kernel (PRE): one raw tile buffer + the pre-split halves
+  // the 12-wave variant's split kernel (PRE): one raw tile buffer + the two parities of the fp16 image
   const int pre = (MLP2_XF + rest) * 4 + MLP2_PRE_HALVES * 2;
   if (ncb > 4 && pre > lds_bytes) lds_bytes = pre;
 }
