@@ -24,6 +24,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "../../include/hpe.h"
 #include "hpe_common.h"
 #include "hpe_dev.h"
@@ -185,9 +188,32 @@ __device__ __forceinline__ void fit_stage(const FitArgs& a, float* xt, const int
   fit_stage_src(a, xt, src, Cin, lane);
 }
 
-template <int KH, int ACT1, bool SPLIT>
-__global__ void __launch_bounds__(FIT_NW * 64) fit_kernel(FitArgs a) {
+// several independent trials in one launch (MULTI): block b runs workgroup (map[b] & 63) of trial
+// (map[b] >> 6), or nothing (map[b] < 0).  The host deals the trials to the 8 lanes blockIdx % 8
+// (hpe_fit_multi_plan), every trial's workgroups in one lane, so each trial still finds itself on
+// one XCD under the round-robin dispatch; the launch-start check below decides per trial.  Nothing
+// crosses trials: each has its own FitArgs (workspace, stats, parameters, optimizer state).
+struct FitEnt {
+  FitArgs a;
+  int G, pad;
+};
+
+// One kernel body, two entries: !MULTI takes its trial in `a` (table / map unused) and works in the
+// blocks with blockIdx % 8 == 0 of an 8 G grid; MULTI loads `a`, G and c through the block map.
+// Everything below the entry works from (a, G, c).
+template <int KH, int ACT1, bool SPLIT, bool MULTI>
+__global__ void __launch_bounds__(FIT_NW * 64) fit_kernel(FitArgs a, const FitEnt* __restrict__ table,
+                                                          const int* __restrict__ map) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  int G, c;
+  if constexpr (MULTI) {
+    const int e = __builtin_amdgcn_readfirstlane(map[blockIdx.x]);
+    if (e < 0) return;
+    const FitEnt* t = table + (e >> 6);  // wave-uniform address: scalar loads into SGPRs
+    a = t->a;
+    G = t->G;
+    c = e & 63;
+  }
   const int* o = a.prog + a.prog[H_OPS_OFF];
   const int Cin = o[O_K], F = o[O_N];
   const int oW = o[O_W], oB = o[O_BIAS], oW2 = o[O_AUX0], oB2 = o[O_AUX1];
@@ -195,10 +221,13 @@ __global__ void __launch_bounds__(FIT_NW * 64) fit_kernel(FitArgs a) {
   const uint32_t thr1 = (uint32_t)o[O_ETHR], thr2 = (uint32_t)o[O_TCOUNT];
   const float keep1 = __int_as_float(o[O_EKEEP]), keep2 = __int_as_float(o[O_F0]);
   const float inv_keep1 = 1.f / keep1;
-  // the grid is 8 G workgroups of which those with blockIdx % 8 == 0 work: under the round-robin
-  // dispatch over the 8 XCDs they share one XCD (speed only: verified below, never assumed)
-  if (blockIdx.x & 7) return;
-  const int G = gridDim.x >> 3, c = blockIdx.x >> 3;
+  if constexpr (!MULTI) {
+    // the grid is 8 G workgroups of which those with blockIdx % 8 == 0 work: under the round-robin
+    // dispatch over the 8 XCDs they share one XCD (speed only: verified below, never assumed)
+    if (blockIdx.x & 7) return;
+    G = gridDim.x >> 3;
+    c = blockIdx.x >> 3;
+  }
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
   const int n = c * 32 + l32;  // this lane's hidden unit (forward / backward)
   const bool nok = n < F;
@@ -780,22 +809,27 @@ __global__ void __launch_bounds__(FIT_NW * 64) fit_kernel(FitArgs a) {
 }
 
 // ---- host side --------------------------------------------------------------------------------
-typedef void (*fit_fn)(FitArgs);
+typedef void (*fit_fn)(FitArgs, const FitEnt*, const int*);
+// one kernel instance <KH, ACT1, SPLIT>: its solo and its multi-trial entry
+struct FitFns {
+  fit_fn solo, multi;
+};
 
 template <int KH, bool SPLIT>
-static fit_fn fit_pick_act(int act) {
-  if (act == ACT_TANH) return fit_kernel<KH, ACT_TANH, SPLIT>;
-  if (act == ACT_SOFTSIGN) return fit_kernel<KH, ACT_SOFTSIGN, SPLIT>;
-  return fit_kernel<KH, -1, SPLIT>;
+static FitFns fit_pick_act(int act) {
+  if (act == ACT_TANH) return {fit_kernel<KH, ACT_TANH, SPLIT, false>, fit_kernel<KH, ACT_TANH, SPLIT, true>};
+  if (act == ACT_SOFTSIGN) return {fit_kernel<KH, ACT_SOFTSIGN, SPLIT, false>, fit_kernel<KH, ACT_SOFTSIGN, SPLIT, true>};
+  return {fit_kernel<KH, -1, SPLIT, false>, fit_kernel<KH, -1, SPLIT, true>};
 }
 
-static fit_fn fit_pick(const int* w, bool split) {
+static FitFns fit_pick_fns(const int* w, bool split) {
   const int* o = w + w[H_OPS_OFF];
   const int kh = ((o[O_K] + 7) & ~7) / 2;
   if (kh == 44) return split ? fit_pick_act<44, true>(o[O_EACT]) : fit_pick_act<44, false>(o[O_EACT]);
   if (kh == 48) return split ? fit_pick_act<48, true>(o[O_EACT]) : fit_pick_act<48, false>(o[O_EACT]);
-  return nullptr;
+  return {nullptr, nullptr};
 }
+static fit_fn fit_pick(const int* w, bool split) { return fit_pick_fns(w, split).solo; }
 
 extern "C" int hpe_fit_supported(const hpe_program* p, int32_t batch) {
   if (!p) return 0;
@@ -835,17 +869,59 @@ extern "C" size_t hpe_fit_workspace_size(const hpe_program* p, int32_t batch) {
   return FIT_PART_OFF * sizeof(int) + (size_t)2 * G * batch * 3 * sizeof(uint64_t);
 }
 
+// argument checks shared by hpe_fit_epoch and hpe_fit_epoch_multi (who: the entry point's name)
+static int fit_check_trial(const hpe_fit_trial& t, const char* who) {
+  if (!t.prog || !t.params || !t.params_t || !t.l2 || !t.tpos || !t.x || !t.y_true || !t.perm || !t.alpha ||
+      !t.stats || !t.workspace)
+    return hpe_fail(HPE_EINVAL, "%s: null argument", who);
+  if (!hpe_fit_supported(t.prog, t.batch))
+    return hpe_fail(HPE_EINVAL, "%s: program / batch %d not supported", who, t.batch);
+  if (t.kind != HPE_OPT_SGD && (!t.m || !t.v)) return hpe_fail(HPE_EINVAL, "%s: Adam/Adamax need m and v", who);
+  if (t.kind < HPE_OPT_SGD || t.kind > HPE_OPT_ADAMAX)
+    return hpe_fail(HPE_EINVAL, "%s: unknown optimizer %d", who, t.kind);
+  if (t.n < 1 || t.n > (int64_t)1 << 30) return hpe_fail(HPE_EINVAL, "%s: bad row count %lld", who, (long long)t.n);
+  return HPE_OK;
+}
+
+// the kernel arguments of one (checked, KIND_MLP2) trial and its workgroup count
+static int fit_fill_args(const hpe_fit_trial& t, FitArgs* out, int* Gout, const char* who) {
+  const int* w = hpe_prog_words(t.prog);
+  const int G = (w[w[H_OPS_OFF] + O_N] + 31) / 32;
+  if (t.stats_stride < 2 + 4 * G)
+    return hpe_fail(HPE_EINVAL, "%s: stats_stride %d < %d", who, t.stats_stride, 2 + 4 * G);
+  FitArgs a = {};
+  a.prog = hpe_prog_dwords(t.prog);
+  a.params = t.params; a.params_t = t.params_t; a.m = t.m; a.v = t.v; a.l2 = t.l2; a.tpos = t.tpos;
+  a.x = t.x; a.ytrue = t.y_true; a.perm = t.perm;
+  a.n = (int)t.n; a.bs = t.batch; a.steps = (int)((t.n + t.batch - 1) / t.batch); a.kind = t.kind;
+  a.b1 = t.beta_1;
+  a.b2 = t.beta_2; a.eps = t.epsilon;
+  a.alpha = t.alpha; a.seed_base = t.seed_base; a.iter0 = t.iter0;
+  a.stats = t.stats; a.stats_stride = t.stats_stride;
+  a.n_train = w[H_NPARAMS_TRAIN];
+  a.n_params = w[H_NPARAMS];
+  a.n_mirror = (int64_t)1 << 40;  // the mirror's size is the compiler's; checked >= 0 only
+  a.n_ws_granules = (int64_t)2 * G * t.batch * 3;
+  a.sync = (int*)t.workspace;
+  a.part = (uint64_t*)((float*)t.workspace + FIT_PART_OFF);
+  {
+    const char* e = getenv("HPE_FIT_FORCE_TIMEOUT");  // tests: the host's timeout rollback
+    a.spin_limit = (e && e[0] == '1') ? -1 : (1 << 22);
+  }
+  *out = a;
+  *Gout = G;
+  return HPE_OK;
+}
+
 extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_t, float* m, float* v,
                              const float* l2, const int32_t* tpos, const float* x, const float* y_true,
                              const int32_t* perm, int64_t n, int32_t batch, int32_t kind, float lr, float beta_1,
                              float beta_2, float epsilon, const float* alpha, uint64_t seed_base, int64_t iter0,
                              float* stats, int32_t stats_stride, int32_t exact, void* workspace, void* stream) {
-  if (!p || !params || !params_t || !l2 || !tpos || !x || !y_true || !perm || !alpha || !stats || !workspace)
-    return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: null argument");
-  if (!hpe_fit_supported(p, batch)) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: program / batch %d not supported", batch);
-  if (kind != HPE_OPT_SGD && (!m || !v)) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: Adam/Adamax need m and v");
-  if (kind < HPE_OPT_SGD || kind > HPE_OPT_ADAMAX) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: unknown optimizer %d", kind);
-  if (n < 1 || n > (int64_t)1 << 30) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: bad row count %lld", (long long)n);
+  const hpe_fit_trial t = {p,    params, params_t, m,      v,       l2,    tpos,      x,     y_true,       perm,     n,
+                           batch, kind,  lr,       beta_1, beta_2,  epsilon, alpha,   seed_base, iter0, stats,
+                           stats_stride, workspace};
+  if (const int rc = fit_check_trial(t, "hpe_fit_epoch")) return rc;
   const int* w = hpe_prog_words(p);
   if (w[H_KIND] == KIND_RES) {
     if (stats_stride < 3) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: stats_stride %d < 3", stats_stride);
@@ -857,27 +933,9 @@ extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_
       return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: residual-stack launch failed");
     return HPE_OK;
   }
-  const int G = (w[w[H_OPS_OFF] + O_N] + 31) / 32;
-  if (stats_stride < 2 + 4 * G) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: stats_stride %d < %d", stats_stride, 2 + 4 * G);
-  FitArgs a = {};
-  a.prog = hpe_prog_dwords(p);
-  a.params = params; a.params_t = params_t; a.m = m; a.v = v; a.l2 = l2; a.tpos = tpos;
-  a.x = x; a.ytrue = y_true; a.perm = perm;
-  a.n = (int)n; a.bs = batch; a.steps = (int)((n + batch - 1) / batch); a.kind = kind;
-  a.b1 = beta_1;
-  a.b2 = beta_2; a.eps = epsilon;
-  a.alpha = alpha; a.seed_base = seed_base; a.iter0 = iter0;
-  a.stats = stats; a.stats_stride = stats_stride;
-  a.n_train = w[H_NPARAMS_TRAIN];
-  a.n_params = w[H_NPARAMS];
-  a.n_mirror = (int64_t)1 << 40;  // the mirror's size is the compiler's; checked >= 0 only
-  a.n_ws_granules = (int64_t)2 * G * batch * 3;
-  a.sync = (int*)workspace;
-  a.part = (uint64_t*)((float*)workspace + FIT_PART_OFF);
-  {
-    const char* e = getenv("HPE_FIT_FORCE_TIMEOUT");  // tests: the host's timeout rollback
-    a.spin_limit = (e && e[0] == '1') ? -1 : (1 << 22);
-  }
+  FitArgs a;
+  int G = 0;
+  if (const int rc = fit_fill_args(t, &a, &G, "hpe_fit_epoch")) return rc;
   hipStream_t s = (hipStream_t)stream;
   // flags and granules: no tag of an earlier launch (an exact re-run, or iterations restored from
   // a checkpoint) can match this launch's
@@ -886,7 +944,151 @@ extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_
   fit_fn k = fit_pick(w, !exact && !hpe_exact_fp32());
   if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess)
     return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
-  hipLaunchKernelGGL(k, dim3(8 * G), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, a);
+  hipLaunchKernelGGL(k, dim3(8 * G), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, a, (const FitEnt*)nullptr, (const int*)nullptr);
   if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: launch failed");
+  return HPE_OK;
+}
+
+// ---- several independent trials in one launch ---------------------------------------------------
+// Placement: trials are dealt to the 8 lanes blockIdx % 8 by decreasing G (ties in input order), each
+// to the first lane of least load, so eight trials go one per lane (one XCD and its L2 each);
+// trial t's workgroup c is block 8 (first_c[t] + c) + lane[t].  Host arithmetic only.
+extern "C" int hpe_fit_multi_plan(const int32_t* groups, int32_t n_trials, int32_t lane_cap, int32_t* lane,
+                                  int32_t* first_c) {
+  if (!groups || !lane || !first_c || n_trials <= 0) return 0;
+  for (int i = 0; i < n_trials; ++i) lane[i] = first_c[i] = -1;
+  for (int i = 0; i < n_trials; ++i)  // a trial that fits no lane can never be placed: the caller's error
+    if (groups[i] < 1 || groups[i] > lane_cap) return 0;
+  std::vector<int> order, ln(n_trials), fc(n_trials);
+  for (int k = n_trials; k >= 1; --k) {  // the longest prefix of the input whose trials all fit
+    order.resize(k);
+    for (int i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return groups[x] > groups[y]; });
+    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool ok = true;
+    for (int t : order) {
+      int l = 0;  // dealt out: the first lane of least load (if that one is full, every lane is)
+      for (int j = 1; j < 8; ++j)
+        if (load[j] < load[l]) l = j;
+      if (load[l] + groups[t] > lane_cap) { ok = false; break; }
+      ln[t] = l;
+      fc[t] = load[l];
+      load[l] += groups[t];
+    }
+    if (!ok) continue;
+    for (int i = 0; i < k; ++i) { lane[i] = ln[i]; first_c[i] = fc[i]; }
+    return k;
+  }
+  return 0;
+}
+
+static size_t fit_multi_map_off(int32_t n_trials) { return ((size_t)n_trials * sizeof(FitEnt) + 15) & ~(size_t)15; }
+
+// the table (FitEnt per trial) and the block map; the map of n trials has at most 8 * 32 n entries
+extern "C" size_t hpe_fit_multi_table_size(int32_t n_trials) {
+  if (n_trials < 1) return 0;
+  return fit_multi_map_off(n_trials) + (size_t)n_trials * 8 * 32 * sizeof(int);
+}
+
+// workgroups per lane that may be resident at once: the launch of 8 * max(lane load) workgroups
+// must fit occupancy x CUs, as in hpe_fit_supported; 0 on failure
+static int fit_multi_cap(fit_fn k) {
+  int dev = 0, cus = 0, occ = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, FIT_NW * 64, FIT_LDS_BYTES) != hipSuccess)
+    return 0;
+  return occ * cus / 8;
+}
+
+extern "C" int hpe_fit_multi_lane_cap(const hpe_program* p) {
+  if (!p) return 0;
+  const int* w = hpe_prog_words(p);
+  if (w[H_KIND] != KIND_MLP2 || w[H_MODE] != MODE_TRAIN) return 0;
+  const FitFns f = fit_pick_fns(w, true);
+  return f.multi ? fit_multi_cap(f.multi) : 0;
+}
+
+// an id of the program's kernel instance (trials of one launch share it), -1 when it has none
+extern "C" int hpe_fit_multi_instance(const hpe_program* p) {
+  if (!p) return -1;
+  const int* w = hpe_prog_words(p);
+  if (w[H_KIND] != KIND_MLP2 || w[H_MODE] != MODE_TRAIN || !fit_pick_fns(w, true).multi) return -1;
+  const int* o = w + w[H_OPS_OFF];
+  const int act = o[O_EACT];
+  return ((o[O_K] + 7) & ~7) / 2 * 4 + (act == ACT_TANH ? 0 : act == ACT_SOFTSIGN ? 1 : 2);
+}
+
+// common kernel instance, workgroup counts and placement of a launch; 0 when it cannot be one launch
+static int fit_multi_prepare(const hpe_fit_trial* trials, int32_t n_trials, bool split, FitFns* fns,
+                             std::vector<int32_t>* G, std::vector<int32_t>* lane, std::vector<int32_t>* first_c) {
+  if (!trials || n_trials < 1) return 0;
+  G->resize(n_trials);
+  lane->resize(n_trials);
+  first_c->resize(n_trials);
+  for (int i = 0; i < n_trials; ++i) {
+    if (!trials[i].prog) return 0;
+    const int* w = hpe_prog_words(trials[i].prog);
+    if (w[H_KIND] != KIND_MLP2 || !hpe_fit_supported(trials[i].prog, trials[i].batch)) return 0;
+    const FitFns f = fit_pick_fns(w, split);
+    if (i == 0) *fns = f;
+    if (!f.multi || f.multi != fns->multi) return 0;
+    (*G)[i] = (w[w[H_OPS_OFF] + O_N] + 31) / 32;
+  }
+  const int cap = fit_multi_cap(fns->multi);
+  return hpe_fit_multi_plan(G->data(), n_trials, cap, lane->data(), first_c->data()) == n_trials;
+}
+
+extern "C" int hpe_fit_multi_supported(const hpe_fit_trial* trials, int32_t n_trials) {
+  FitFns fns;
+  std::vector<int32_t> G, lane, first_c;
+  return fit_multi_prepare(trials, n_trials, true, &fns, &G, &lane, &first_c);
+}
+
+extern "C" int hpe_fit_epoch_multi(const hpe_fit_trial* trials, int32_t n_trials, int32_t exact, void* table,
+                                   void* stream) {
+  if (!trials || !table || n_trials < 1) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch_multi: null argument");
+  for (int i = 0; i < n_trials; ++i) {
+    if (const int rc = fit_check_trial(trials[i], "hpe_fit_epoch_multi")) return rc;
+    if (hpe_prog_words(trials[i].prog)[H_KIND] != KIND_MLP2)
+      return hpe_fail(HPE_EINVAL, "hpe_fit_epoch_multi: trial %d: residual-stack programs run alone (hpe_fit_epoch)", i);
+  }
+  FitFns fns;
+  std::vector<int32_t> G, lane, first_c;
+  if (!fit_multi_prepare(trials, n_trials, !exact && !hpe_exact_fp32(), &fns, &G, &lane, &first_c))
+    return hpe_fail(HPE_EINVAL, "hpe_fit_epoch_multi: the %d trials do not share one kernel instance (input width, "
+                                "activation class) or do not fit one launch (hpe_fit_multi_plan)", n_trials);
+  int load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, depth = 0;
+  for (int i = 0; i < n_trials; ++i) load[lane[i]] += G[i];
+  for (int l = 0; l < 8; ++l) depth = std::max(depth, load[l]);
+  const int grid = 8 * depth;
+  const size_t map_off = fit_multi_map_off(n_trials), bytes = map_off + (size_t)grid * sizeof(int);
+  if (bytes > hpe_fit_multi_table_size(n_trials)) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: map size");
+  std::vector<unsigned char> host(bytes, 0);
+  FitEnt* ent = (FitEnt*)host.data();
+  int* map = (int*)(host.data() + map_off);
+  for (int b = 0; b < grid; ++b) map[b] = -1;
+  for (int i = 0; i < n_trials; ++i) {
+    int g = 0;
+    if (const int rc = fit_fill_args(trials[i], &ent[i].a, &g, "hpe_fit_epoch_multi")) return rc;
+    ent[i].G = g;
+    for (int c = 0; c < g; ++c) map[8 * (first_c[i] + c) + lane[i]] = i * 64 + c;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // the staging vector dies on return, so the copy is complete before it does: ordered on the
+  // stream after whatever still reads the table, then waited for
+  if (hipMemcpyAsync(table, host.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: table copy: %s", hipGetErrorString(hipGetLastError()));
+  for (int i = 0; i < n_trials; ++i)  // flags and granules, as hpe_fit_epoch
+    if (hipMemsetAsync(trials[i].workspace, 0, hpe_fit_workspace_size(trials[i].prog, trials[i].batch), s) != hipSuccess)
+      return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: memset: %s", hipGetErrorString(hipGetLastError()));
+  if (hipFuncSetAttribute((const void*)fns.multi, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess)
+    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
+  hipLaunchKernelGGL(fns.multi, dim3(grid), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, FitArgs{}, (const FitEnt*)table,
+                     (const int*)((const unsigned char*)table + map_off));
+  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: launch failed");
   return HPE_OK;
 }

@@ -36,6 +36,12 @@ SIGNATURES = {
     'hpe_fit_workspace_size': (_sz, [_vp, _i32]),
     'hpe_fit_epoch': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f,
                                      _f, _f, _f, _vp, _u64, _i64, _vp, _i32, _i32, _vp, _vp]),
+    'hpe_fit_multi_plan': (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    'hpe_fit_multi_lane_cap': (ctypes.c_int, [_vp]),
+    'hpe_fit_multi_instance': (ctypes.c_int, [_vp]),
+    'hpe_fit_multi_table_size': (_sz, [_i32]),
+    'hpe_fit_multi_supported': (ctypes.c_int, [_vp, _i32]),
+    'hpe_fit_epoch_multi': (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'hpe_blazeface_create': (ctypes.c_int, [_vp, _i64, ctypes.POINTER(_vp)]),
     'hpe_blazeface_destroy': (ctypes.c_int, [_vp]),
     'hpe_blazeface_workspace_size': (_sz, [_vp, _i64]),
@@ -86,6 +92,16 @@ SIGNATURES = {
     'hpe_rccl_allreduce': (ctypes.c_int, [_vp, _i64, _vp, _vp]),
 }
 RCCL_ID_BYTES = 128   # HPE_RCCL_ID_BYTES
+
+
+class FitTrial(ctypes.Structure):
+    """hpe_fit_trial: hpe_fit_epoch's arguments of one trial of hpe_fit_epoch_multi."""
+    _fields_ = [('prog', _vp), ('params', _vp), ('params_t', _vp), ('m', _vp), ('v', _vp), ('l2', _vp),
+                ('tpos', _vp), ('x', _vp), ('y_true', _vp), ('perm', _vp), ('n', _i64), ('batch', _i32),
+                ('kind', _i32), ('lr', _f), ('beta_1', _f), ('beta_2', _f), ('epsilon', _f), ('alpha', _vp),
+                ('seed_base', _u64), ('iter0', _i64), ('stats', _vp), ('stats_stride', _i32),
+                ('workspace', _vp)]
+
 
 _lib = None
 _CSRC = os.path.join(os.path.dirname(_HERE), 'csrc')

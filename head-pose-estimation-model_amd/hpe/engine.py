@@ -352,7 +352,7 @@ class Engine:
             return 1
         return -(-int(prog.info['F']) // 32)
 
-    def _alphas(self, opt, steps):
+    def _alphas_host(self, opt, steps):
         """Per-iteration optimizer step sizes, computed exactly as hpe_optim_step does (double
         arithmetic on the float32 hyper-parameters, rounded to float32)."""
         t = (self.iterations + 1 + np.arange(steps)).astype(np.float64)
@@ -365,11 +365,41 @@ class Engine:
             a = lr / (1.0 - b1 ** t)
         else:
             a = np.full(steps, lr)
-        return torch.from_numpy(a.astype(np.float32)).to(self.device)
+        return a.astype(np.float32)
+
+    def _alphas(self, opt, steps):
+        return torch.from_numpy(self._alphas_host(opt, steps)).to(self.device)
 
     def _restore(self, saved):
         for dst, src in zip([t for t in (self.params, self.params_t, self.m, self.v) if t is not None], saved):
             dst.copy_(src)
+
+    # -- one trial of a multi-trial epoch launch (hpe/trials.py, hpe_fit_epoch_multi) -------------
+    def fit_state(self):
+        """The tensors an epoch launch updates in place (what a flagged epoch restores)."""
+        return [t for t in (self.params, self.params_t, self.m, self.v) if t is not None]
+
+    def fit_flag_word(self):
+        """The flags word of this engine's epoch-launch workspace (device int32 [1])."""
+        return self._fit_ws[1:2].view(torch.int32)
+
+    def fit_trial(self, opt, x, y, perm, batch, stats, seed_base, alpha):
+        """hpe_fit_trial of this engine's next epoch: fit_epoch's arguments, with alpha (device
+        [steps], the values of _alphas_host) supplied by the caller."""
+        c = self.program('train', 1)
+        kind = OPT_KIND[opt.kind]
+        if kind and self.m is None:
+            self.m = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
+            self.v = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
+        need = _lib.load().hpe_fit_workspace_size(c.h, int(batch))
+        if getattr(self, '_fit_ws', None) is None or self._fit_ws.numel() * 4 < need:
+            self._fit_ws = torch.zeros(max(need // 4, 16), dtype=torch.float32, device=self.device)
+        dp = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        return _lib.FitTrial(c.h.value, dp(self.params), dp(self.params_t), dp(self.m), dp(self.v), dp(self.l2),
+                             dp(self.tpos), dp(x), dp(y), dp(perm), int(perm.numel()), int(batch), kind,
+                             float(opt.learning_rate), float(opt.beta_1), float(opt.beta_2), float(opt.epsilon),
+                             dp(alpha), int(seed_base) & 0xFFFFFFFFFFFFFFFF, int(self.iterations), dp(stats),
+                             int(stats.shape[1]), dp(self._fit_ws))
 
     def fit_epoch(self, opt, x, y, perm, batch, stats, seed_base):
         """One epoch of fit: ceil(n / batch) steps over rows perm (device int32) of x / y in one

@@ -25,6 +25,24 @@ from .parallel import all_reduce_grad, batch_slice
 KERAS_VERSION = '2.13.1'
 
 
+def epoch_logs(stats, nbs, n, P, val=None):
+    """One epoch's Keras logs from the per-step stats [steps, 2 + k] (sse, sae, regularisation
+    shares) of batches of nbs rows: batch-size-weighted means over the n images of P pixels.
+    val: None, or (validation [sse, sae], element count, regularisation loss).  Shared by Model.fit
+    and hpe.fit_many."""
+    st = np.asarray(stats).astype(np.float64)
+    nbs = np.asarray(nbs, dtype=np.float64)
+    loss = float((st[:, 0].sum() / (P * 3) + (nbs * st[:, 2:].sum(axis=1)).sum()) / n)
+    mae = float(st[:, 1].sum() / (n * P * 3))
+    logs = {'loss': loss, 'mae': mae}
+    if val is not None:
+        vs, vc, reg = val
+        vs = np.asarray(vs).astype(np.float64)
+        logs['val_loss'] = float(vs[0] / vc + reg)
+        logs['val_mae'] = float(vs[1] / vc)
+    return logs
+
+
 class Model:
     def __init__(self, inputs=None, outputs=None, name=None, _config=None, _weights=None):
         self.name = name or L.unique_name('model')
@@ -302,16 +320,10 @@ class Model:
                 if world > 1:
                     all_reduce_grad(eng.grad, self._dist[1])
                 eng.optimizer_step(self.optimizer, stats[s])
-            st = stats.cpu().numpy().astype(np.float64)
-            nbs = np.asarray(nbs, dtype=np.float64)
-            loss = float((st[:, 0].sum() / (P * 3) + (nbs * st[:, 2:].sum(axis=1)).sum()) / n)
-            mae = float(st[:, 1].sum() / (n * P * 3))
-            logs = {'loss': loss, 'mae': mae}
+            st, val = stats.cpu().numpy(), None
             if validation_data is not None:
-                vs = eng.loss_sums(vxd, vyd, vP).cpu().numpy().astype(np.float64)
-                vc = vn * vP * 3
-                logs['val_loss'] = float(vs[0] / vc + self._reg_loss())
-                logs['val_mae'] = float(vs[1] / vc)
+                val = (eng.loss_sums(vxd, vyd, vP).cpu().numpy(), vn * vP * 3, self._reg_loss())
+            logs = epoch_logs(st, nbs, n, P, val)
             self.optimizer.iterations = eng.iterations
             if verbose and verbose != 0:
                 print('Epoch %d/%d - ' % (epoch + 1, epochs) +

@@ -191,6 +191,56 @@ int hpe_fit_epoch(const hpe_program *prog, float *params, float *params_t, float
                   float *stats, int32_t stats_stride, int32_t exact, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Several independent trainings ("trials") in ONE epoch launch.  hpe_fit_epoch uses one workgroup
+ * per 32 hidden units in the blocks with blockIdx % 8 == 0 of an 8 G grid; the other seven eighths
+ * of that grid carry further trials here, each a closed group of workgroups running the same
+ * per-trial arithmetic as hpe_fit_epoch (bit-identical results).  Nothing crosses trials: each has
+ * its own parameters, optimizer state, permutation, seeds, stats and workspace (with its own flags
+ * word [1], as above).  hpe_fit_trial holds hpe_fit_epoch's arguments of one trial.
+ *
+ * hpe_fit_multi_plan (host arithmetic only, no device call): deals trials with groups[i] = G_i
+ * workgroups to the 8 lanes blockIdx % 8 by decreasing G (ties in input order), each to the first
+ * lane of least load that still fits it (eight trials go one per lane), a lane holding at most
+ * lane_cap workgroups; trial i's workgroup c is block 8 (first_c[i] + c) + lane[i].
+ * Returns the number of trials placed: the longest prefix of the input that fits one launch (the
+ * rest, lane = first_c = -1, is for a later launch); 0 if some G_i is < 1 or > lane_cap.
+ * hpe_fit_multi_lane_cap: lane_cap of the current device for prog's kernel (occupancy x CUs / 8:
+ * the whole grid of 8 max(lane load) workgroups is resident at once).  hpe_fit_multi_instance: an
+ * id of prog's kernel instance (input width 88 / 96, activation class tanh / softsign / other), -1
+ * if hpe_fit_epoch_multi cannot run it; all trials of one launch must share it.
+ * hpe_fit_multi_supported: 1 if every trial passes hpe_fit_supported for its batch, none is a
+ * residual stack, all share one instance and the plan places all of them.
+ * hpe_fit_epoch_multi: one launch for all trials (HPE_EINVAL if !hpe_fit_multi_supported); zeroes
+ * every trial's workspace first.  table: hpe_fit_multi_table_size(n_trials) bytes of device memory,
+ * written here through the stream (the call waits for that copy; the table must stay untouched
+ * until the launch has finished). */
+typedef struct hpe_fit_trial {
+  const hpe_program *prog;
+  float *params, *params_t, *m, *v;
+  const float *l2;
+  const int32_t *tpos;
+  const float *x, *y_true;
+  const int32_t *perm;
+  int64_t n;
+  int32_t batch, kind;
+  float lr, beta_1, beta_2, epsilon;
+  const float *alpha;
+  uint64_t seed_base;
+  int64_t iter0;
+  float *stats;
+  int32_t stats_stride;
+  void *workspace;
+} hpe_fit_trial;
+int hpe_fit_multi_plan(const int32_t *groups, int32_t n_trials, int32_t lane_cap, int32_t *lane,
+                       int32_t *first_c);
+int hpe_fit_multi_lane_cap(const hpe_program *prog);
+int hpe_fit_multi_instance(const hpe_program *prog);
+size_t hpe_fit_multi_table_size(int32_t n_trials);
+int hpe_fit_multi_supported(const hpe_fit_trial *trials, int32_t n_trials);
+int hpe_fit_epoch_multi(const hpe_fit_trial *trials, int32_t n_trials, int32_t exact, void *table,
+                        void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BlazeFace backbone — replaces the TF call on the fused BlazeFace+regressor
  * graph, `self.model.predict(...)` at BlazePoser/blazeFaceDetectorH5.py:272, for a whole batch.
  * words: the plan hpe/blazeface.py builds from the unified model's model_config (csrc/hpe_prog.h

@@ -11,6 +11,8 @@ BIWI_Test_Enlarged_features_88, where stoqa9pt scores 7.8100 / 3.4456 (BASELINE.
 BIWI_Train_Enlarged_features_88 (10,284 rows); the reference also concatenated
 BIWI_NoTrack_Enlarged_features_88, which is absent from the reference checkout.  One run per seed on
 this GPU through Model.fit (fused epoch launches).  Writes gpurun_out/seed_spread_88.json.
+With --together all seeds train side by side through hpe.fit_many instead (several per epoch
+launch, the same results per seed).
 
 `python scripts/seed_spread_88.py <seeds> steps` instead trains every seed for stoqa9pt's own
 770,868 SGD steps with EarlyStopping off (match the checkpoint's run length) and writes
@@ -74,7 +76,7 @@ def load(name):
     return d['features'].reshape(-1, 1, 1, 88).astype(np.float32), d['poses'].reshape(-1, 1, 1, 3)
 
 
-def main(seeds, max_epochs, match_steps=False):
+def main(seeds, max_epochs, match_steps=False, together=False):
     import hpe
     from hpe import keras
     from hpe.data import train_test_split
@@ -84,17 +86,34 @@ def main(seeds, max_epochs, match_steps=False):
     bx, by = load('BIWI_Test_Enlarged_features_88_0.7_1.npz')
     runs = []
     os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-    for s in seeds:
-        hpe.set_seed(s)
-        keras.backend.clear_session()
-        m = create_model(keras)
+    def callbacks():
         cbs = [Progress()]
         if not match_steps:
             cbs.insert(0, keras.callbacks.EarlyStopping(monitor='val_loss', patience=40, min_delta=0.001,
                                                         restore_best_weights=True))
+        return cbs
+
+    ms, hs = [], []
+    if together:    # every seed's model initialised under its own seed, then one fit_many
+        for s in seeds:
+            hpe.set_seed(s)
+            keras.backend.clear_session()
+            ms.append(create_model(keras))
         t0 = time.perf_counter()
-        h = m.fit(tx, ty, epochs=max_epochs, batch_size=128, validation_data=(vx, vy), callbacks=cbs, verbose=0)
-        dt = time.perf_counter() - t0
+        hs = hpe.fit_many(ms, tx, ty, 128, epochs=max_epochs, seeds=seeds, validation_data=(vx, vy),
+                          callbacks=[callbacks() for _ in seeds])
+        dts = [(time.perf_counter() - t0) / len(seeds)] * len(seeds)   # the call's time, shared equally
+    for i, s in enumerate(seeds):
+        if together:
+            m, h, dt = ms[i], hs[i], dts[i]
+        else:
+            hpe.set_seed(s)
+            keras.backend.clear_session()
+            m = create_model(keras)
+            t0 = time.perf_counter()
+            h = m.fit(tx, ty, epochs=max_epochs, batch_size=128, validation_data=(vx, vy), callbacks=callbacks(),
+                      verbose=0)
+            dt = time.perf_counter() - t0
         _, a_mae = m.evaluate(ax, ay, verbose=0)
         _, b_mae = m.evaluate(bx, by, verbose=0)
         ep = len(h.history['loss'])
@@ -124,9 +143,11 @@ def main(seeds, max_epochs, match_steps=False):
 STOQA9PT_STEPS = 770868
 
 if __name__ == '__main__':
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-    if len(sys.argv) > 2 and sys.argv[2] == 'steps':
+    together = '--together' in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != '--together']
+    n = int(args[0]) if args else 4
+    if len(args) > 1 and args[1] == 'steps':
         # 8,227 training rows -> 65 steps per epoch at batch 128
-        main(list(range(n)), -(-STOQA9PT_STEPS // 65), match_steps=True)
+        main(list(range(n)), -(-STOQA9PT_STEPS // 65), match_steps=True, together=together)
     else:
-        main(list(range(n)), int(sys.argv[2]) if len(sys.argv) > 2 else 15000)
+        main(list(range(n)), int(args[1]) if len(args) > 1 else 15000, together=together)

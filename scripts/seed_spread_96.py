@@ -6,7 +6,8 @@ train_96.py's own loop (Model-96/train_96.py:42-57 config, :142-183 split / call
 Adam lr 2.8e-4, batch 128, 80/20 train_test_split(random_state=42), EarlyStopping(val_loss,
 patience 40, min_delta 1e-3, restore_best_weights), then evaluate on AFLW2000_features_96 and
 BIWI_Test_Enlarged_features_96.  One run per seed (weight init + shuffles), all on this GPU through
-Model.fit (fused epoch launches).
+Model.fit (fused epoch launches), one after another; with --together all seeds train side by side
+through hpe.fit_many (several per epoch launch, the same results per seed).
 
 The reference's training set BIWI_train_features_96.npz is a missing blob in the reference
 checkout, so the substitute is BIWI_Train_Enlarged_features_96_0.7_1.npz (1,643 rows).  The result
@@ -42,7 +43,7 @@ def load(name):
     return d['features'].reshape(-1, 1, 1, 96).astype(np.float32), d['poses'].reshape(-1, 1, 1, 3)
 
 
-def main(seeds, max_epochs):
+def main(seeds, max_epochs, together=False):
     import hpe
     from hpe import keras
     from hpe.data import train_test_split
@@ -52,15 +53,31 @@ def main(seeds, max_epochs):
     bx, by = load('BIWI_Test_Enlarged_features_96_0.7_1.npz')
     runs = []
     os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-    for s in seeds:
-        hpe.set_seed(s)
-        keras.backend.clear_session()
-        m = create_model(keras)
-        es = keras.callbacks.EarlyStopping(monitor='val_loss', patience=40, min_delta=0.001,
-                                           restore_best_weights=True)
+    def early_stop():
+        return keras.callbacks.EarlyStopping(monitor='val_loss', patience=40, min_delta=0.001,
+                                             restore_best_weights=True)
+
+    ms, hs = [], []
+    if together:    # every seed's model initialised under its own seed, then one fit_many
+        for s in seeds:
+            hpe.set_seed(s)
+            keras.backend.clear_session()
+            ms.append(create_model(keras))
         t0 = time.perf_counter()
-        h = m.fit(tx, ty, epochs=max_epochs, batch_size=128, validation_data=(vx, vy), callbacks=[es], verbose=0)
-        dt = time.perf_counter() - t0
+        hs = hpe.fit_many(ms, tx, ty, 128, epochs=max_epochs, seeds=seeds, validation_data=(vx, vy),
+                          callbacks=[[early_stop()] for _ in seeds])
+        dts = [(time.perf_counter() - t0) / len(seeds)] * len(seeds)   # the call's time, shared equally
+    for i, s in enumerate(seeds):
+        if together:
+            m, h, dt = ms[i], hs[i], dts[i]
+        else:
+            hpe.set_seed(s)
+            keras.backend.clear_session()
+            m = create_model(keras)
+            t0 = time.perf_counter()
+            h = m.fit(tx, ty, epochs=max_epochs, batch_size=128, validation_data=(vx, vy), callbacks=[early_stop()],
+                      verbose=0)
+            dt = time.perf_counter() - t0
         _, a_mae = m.evaluate(ax, ay, verbose=0)
         _, b_mae = m.evaluate(bx, by, verbose=0)
         pa = m.predict(ax).reshape(-1, 3)
@@ -84,5 +101,6 @@ def main(seeds, max_epochs):
 
 
 if __name__ == '__main__':
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-    main(list(range(n)), int(sys.argv[2]) if len(sys.argv) > 2 else 10000)
+    args = [a for a in sys.argv[1:] if a != '--together']
+    n = int(args[0]) if args else 8
+    main(list(range(n)), int(args[1]) if len(args) > 1 else 10000, together='--together' in sys.argv[1:])
