@@ -10,7 +10,7 @@ import torch
 import hpe
 from hpe import keras
 from oracle import keras_ref as K
-from util import ATOL, RTOL, DATA, features, fixture, index, input_channels, labels
+from util import ATOL, RTOL, DATA, data_grad64, features, fixture, index, input_channels, labels
 
 pytestmark = pytest.mark.gpu
 
@@ -236,21 +236,7 @@ def test_chain_split_precision_and_overflow_guard():
     np.testing.assert_allclose(eng.forward(xt, 1).cpu().numpy(), ref, rtol=RTOL, atol=ATOL)
 
 
-def _data_grad64(mc, w, x, y, layout, seed):
-    """float64 oracle gradient of the data term (mse) in the engine's flat parameter order."""
-    g = K.Graph(mc, w)
-    tr = list(g.trainable)
-    for k in tr:
-        g.params[k].requires_grad_(True)
-    p = g.forward(x, training=True, drop_seed=seed)
-    yt = torch.tensor(np.asarray(y), dtype=torch.float64)
-    yb = yt.reshape(yt.shape[0], *([1] * (p.dim() - 2)), 3).expand_as(p)
-    gr = torch.autograd.grad(K.mse(yb, p), [g.params[k] for k in tr])
-    flat = np.zeros(sum(int(np.prod(s)) for _, s in layout.param_index.values()))
-    for k, gk in zip(tr, gr):
-        o, shp = layout.param_index[k]
-        flat[o:o + int(np.prod(shp))] = gk.detach().numpy().ravel()
-    return flat
+_data_grad64 = data_grad64   # the float64 oracle gradient (tests/util.py), under its name here
 
 
 @pytest.mark.parametrize('rid,P', [('sqnu665j', 1), ('sqnu665j', 96 * 96), ('stoqa9pt', 4 * 4)])
