@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "hpe_common.h"
 #include "hpe_dev.h"
@@ -154,6 +155,11 @@ __device__ __forceinline__ int lane_now() {
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
 }
+// the value of lane l ^ 32, l the caller's lane_now(): __shfl_xor's own lane id (and the bound it
+// derives from it) is one value for the whole kernel, carried from the first shuffle to the last
+__device__ __forceinline__ float xor32_now(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute((l ^ 32) << 2, __float_as_int(v)));
+}
 
 // Staging of the contiguous-rows instantiation (no gather, P >= 32; mlp2_kernel<..., CONTIG>): tp is
 // the tile's first row in HBM, carried by the tile loop (no 64-bit row * C_in product per piece), ti
@@ -247,6 +253,21 @@ __device__ __forceinline__ bool presplit_tile(const float* xs, _Float16* xf, int
   return out;
 }
 
+// split_w8 (hpe_common.h) for the pre-split kernel's dZ1, same bits: the scaled remainder C (v - f32(h))
+// as fma(f32(h), -C, C v) — C is a power of two and v - f32(h) is exact in fp32, so C v, C f32(h) and
+// the result are all exact — which hipcc selects as one v_fma_mix_f32 reading the fp16 half in
+// place: no v_cvt_f32_f16 back-conversion per value (presplit_tile's split_d8 gets the same
+// instruction from contracting its own multiply)
+__device__ __forceinline__ SplitW split_w8_mix(f32x8 v) {
+  SplitW r;
+  r.h = __builtin_convertvector(v, h8);
+  f32x8 lo;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) lo[j] = __builtin_fmaf((float)r.h[j], -SPLIT_C, v[j] * SPLIT_C);
+  r.cl = __builtin_convertvector(lo, h8);
+  return r;
+}
+
 // NWM: launch bound in waves (12: any width <= 384, 168-VGPR budget; 4: F <= 128, 256 budget)
 // SPLIT: both GEMMs on fp16 MFMA at fp32 accuracy (split_w8 / split_d8 / mfma3_dw, hpe_common.h:
 //   exponent-shifted lo halves, X the 3-fragment data side, accumulators at scale SPLIT_C), same registers:
@@ -283,6 +304,8 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   // carries no per-value selects for its pad columns; the runtime-activation variant keeps them
   // (sigmoid(0) != 0)
   constexpr bool LEAN = PRE && ACT1 >= 0;
+  // EXPK: the exponent's constant of the compiled-in tanh rides on the per-unit scalars (colt)
+  constexpr bool EXPK = PRE && ACT1 == ACT_TANH;
   // A1 park in the bank-quad slots of a1_row; the 4-wave kernel pays for the padding with 3-float loss
   // accumulators (HS: [NT][3], 128 floats fewer at NT = 128) so it keeps four workgroups per CU — the
   // 12-wave one keeps [NT][4] (3-float rows there push its tile loop over the VGPR budget)
@@ -389,7 +412,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         mx = fmaxf(mx, fabsf(v[s][j]));
       }
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    mx = fmaxf(mx, PRE ? xor32_now(mx, lane_now()) : __shfl_xor(mx, 32, 64));
     const float s1 = pow2_scale(mx, 13);
     inv1 = SPLIT_INV_C / s1;
 #pragma unroll
@@ -424,7 +447,12 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     // the per-unit scalars live in LDS across the tile loop, not in 3 loop-carried VGPRs (the
     // 12-wave variant sits at the 168-VGPR budget; in registers they pushed a W1 fragment to scratch)
     const float b1 = (nok && o_bias >= 0) ? b1r : 0.f;
-    if (half == 0) *(f32x4*)(colt + n * 4) = f32x4{inv1, b1, s2, 0.f};
+    // EXPK: the pre-split kernel with tanh compiled in keeps the pair pre-multiplied by fast_tanh5's
+    // 2 log2(e), so the forward takes e^{2z} = exp2(fma(acc, inv1 k, b1 k)) without a multiply per
+    // value (inv1 is a power of two: inv1 k is exact; b1 k rounds once, the argument moves by about
+    // one ulp of itself, inside fast_tanh5's 2^-22 absolute bar)
+    const float ck = EXPK ? 2.8853900817779268f : 1.f;
+    if (half == 0) *(f32x4*)(colt + n * 4) = f32x4{inv1 * ck, b1 * ck, s2, 0.f};
   }
   // small tables in LDS rather than loop-carried VGPRs (the 12-wave variant is at its budget)
 #pragma unroll
@@ -478,6 +506,12 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     const int tlane = PRE ? lane_now() : lane, thalf = tlane >> 5, tl32 = tlane & 31;
     const int tcol = wave * 32 + tl32;
     const bool tok = tcol < F;
+    // ... and the thread id of the head phase with them: threadIdx.x, the LDS addresses and the
+    // cold-path terms (output pointer, dropout hash) derived from it are otherwise carried around
+    // the loop, in scratch at this budget
+    // (threadIdx.x itself, unsigned as ever, in the other kernels: their code stays as it was)
+    using tid_t = typename std::conditional<PRE, int, unsigned>::type;
+    const tid_t ttid = PRE ? (tid_t)(wave * 64 + tlane) : (tid_t)threadIdx.x;
     const int64_t row0 = (int64_t)tile * T;
     const float* xs = xbuf + (PRE ? 0 : buf) * MLP2_XF;
     const float* lab = lbuf + buf * MLP2_LAB;
@@ -575,10 +609,16 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
           }
         }
       }
-      const f32x4 cs = *(const f32x4*)(colt + tcol * 4);  // (inv1, b1, s2, -)
+      const f32x4 cs = *(const f32x4*)(colt + tcol * 4);  // (inv1, b1, s2, -); EXPK: both x 2 log2(e)
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        float z = act1_f<ACT1, SPLIT>(e1.act, SPLIT ? fmaf(acc[g], cs.x, cs.y) : acc[g] + cs.y);
+        float z;
+        if constexpr (EXPK) {  // fast_tanh5 with its argument already scaled
+          const float e = __builtin_amdgcn_exp2f(fmaf(acc[g], cs.x, cs.y));
+          z = fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + e), 1.f);
+        } else {
+          z = act1_f<ACT1, SPLIT>(e1.act, SPLIT ? fmaf(acc[g], cs.x, cs.y) : acc[g] + cs.y);
+        }
         if (DROP) z = (dmask >> g) & 1u ? z * inv_keep1 : 0.f;
         // LEAN: a pad column (n >= F) has a zero W1 column, b1 = 0 and zero W2 rows, and the
         // compiled-in activations map 0 to 0: its z is already exactly 0 without a select
@@ -609,9 +649,15 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
             s2 = fmaf(av[e], w.z, s2);
           }
         }
-        s0 += __shfl_xor(s0, 32, 64);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
+        if constexpr (PRE) {
+          s0 += xor32_now(s0, tlane);
+          s1 += xor32_now(s1, tlane);
+          s2 += xor32_now(s2, tlane);
+        } else {
+          s0 += __shfl_xor(s0, 32, 64);
+          s1 += __shfl_xor(s1, 32, 64);
+          s2 += __shfl_xor(s2, 32, 64);
+        }
         if (thalf == 0) *(f32x4*)(part + (wave * T + r) * 4) = f32x4{s0, s1, s2, 0.f};
       }
     }
@@ -624,7 +670,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
     STAMP(5);
     if constexpr (PRE) {
       if (wave >= 2 && tile + gridDim.x < ntiles)
-        bad |= presplit_tile<KH>(xbuf, xfb + (buf ^ 1) * MLP2_IMG, threadIdx.x - 128, NT - 128);
+        bad |= presplit_tile<KH>(xbuf, xfb + (buf ^ 1) * MLP2_IMG, ttid - 128, NT - 128);
     }
 
     // ---- head: sum partials (fixed wave order) + b2, epilogue, loss / output ----
@@ -640,9 +686,9 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       float lv = 0.f, ha0 = 0.f, ha1 = 0.f, ha2 = 0.f;
       if (mode != MODE_FWD) {
         lv = lab[r * 4 + j];
-        ha0 = hacc[threadIdx.x * HS + 0];
-        ha1 = hacc[threadIdx.x * HS + 1];
-        ha2 = hacc[threadIdx.x * HS + 2];
+        ha0 = hacc[ttid * HS + 0];
+        ha1 = hacc[ttid * HS + 1];
+        ha2 = hacc[ttid * HS + 2];
       }
 #pragma unroll
       for (int w = 0; w < MLP2_MAXW; ++w) z += pv[w];
@@ -672,14 +718,14 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
           dz2[r * 4 + j] = g;
           ha2 += g;
         }
-        hacc[threadIdx.x * HS + 0] = ha0;
-        hacc[threadIdx.x * HS + 1] = ha1;
-        hacc[threadIdx.x * HS + 2] = ha2;
+        hacc[ttid * HS + 0] = ha0;
+        hacc[ttid * HS + 1] = ha1;
+        hacc[ttid * HS + 2] = ha2;
       }
     };
     if constexpr (NWM == MLP2_MAXW) {
       // at least 320 threads for the 96 items: one item per thread
-      if (threadIdx.x < T * 3) head_item(threadIdx.x);
+      if (ttid < T * 3) head_item(ttid);
     } else {
       for (int it = threadIdx.x; it < T * 3 && threadIdx.x < NT3; it += NT3) head_item(it);
     }
@@ -752,19 +798,18 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         f32x8 dv0, dv1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv0[j] = dz_of(j);
-        const SplitW d0 = split_w8(dv0);
+        const SplitW d0 = split_w8_mix(dv0);
         __builtin_amdgcn_sched_barrier(0);
-        // (the fence after block 0 keeps the 18 reads of this K-step from all being in flight at once:
-        // without it their 36 VGPRs push a W1 fragment to scratch, reloaded per tile in the forward)
+        // (no fence between the blocks: all 18 reads of the K-step may be in flight at once.  Their 36
+        // VGPRs fit since the head phase's thread id and the shuffles' lane id are recomputed per tile
+        // (ttid, xor32_now) instead of carried around the loop; a fence after block 0, which the
+        // tighter budget needed before, measured 1.2 % slower on the Model-96 step, A/B x3)
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-          dw[kb] = mfma3_dw(xt_of(0, kb), d0, dw[kb]);
-          if (kb == 0) __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int kb = 0; kb < NKB; ++kb) dw[kb] = mfma3_dw(xt_of(0, kb), d0, dw[kb]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) dv1[j] = dz_of(8 + j);
         __builtin_amdgcn_sched_barrier(0);
-        const SplitW d1 = split_w8(dv1);
+        const SplitW d1 = split_w8_mix(dv1);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) dw[kb] = mfma3_dw(xt_of(1, kb), d1, dw[kb]);
       } else if constexpr (SPLIT) {
