@@ -290,11 +290,13 @@ int chain_launch(const int* words_host, const Args& a, int grid, hipStream_t s);
 int res_supported(const int* words);
 int res_grid_cap(int n_cu);
 int res_launch(const int* words_host, const Args& a, int grid, hipStream_t s);
-int res_fit_launch(const int* w, const int* dwords, float* params, float* params_t, float* m, float* v,
-                   const float* l2, const int32_t* tpos, const float* x, const float* y_true, const int32_t* perm,
-                   int64_t n, int32_t batch, int32_t kind, float beta_1, float beta_2, float epsilon,
-                   const float* alpha, uint64_t seed_base, int64_t iter0, float* stats, int32_t stats_stride,
-                   void* workspace, hipStream_t s);
+struct hpe_fit_trial;  // include/hpe.h
+int res_fit_launch(const hpe_fit_trial& t, hipStream_t s);
+// several trials in one launch (block b trains trial b): the kernel-instance id of a program's word
+// stream (-1: none), the bytes of an n-trial argument table, and the launch itself
+int res_fit_instance(const int* words);
+size_t res_fit_table_bytes(int n_trials);
+int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s);
 
 // a program's word stream: host copy (kernel geometry) and device copy (kernel argument)
 struct hpe_program;

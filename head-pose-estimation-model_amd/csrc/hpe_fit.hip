@@ -928,8 +928,7 @@ extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(workspace, 0, hpe_fit_workspace_size(p, batch), s) != hipSuccess)
       return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: memset: %s", hipGetErrorString(hipGetLastError()));
-    if (res_fit_launch(w, hpe_prog_dwords(p), params, params_t, m, v, l2, tpos, x, y_true, perm, n, batch, kind,
-                       beta_1, beta_2, epsilon, alpha, seed_base, iter0, stats, stats_stride, workspace, s))
+    if (res_fit_launch(t, s))
       return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: residual-stack launch failed");
     return HPE_OK;
   }
@@ -1091,4 +1090,42 @@ extern "C" int hpe_fit_epoch_multi(const hpe_fit_trial* trials, int32_t n_trials
                      (const int*)((const unsigned char*)table + map_off));
   if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: launch failed");
   return HPE_OK;
+}
+
+// ---- several residual stacks in one launch (csrc/hpe_res.hip: block b trains trial b) --------------
+// the instance id from a word stream alone (what hpe_program_create was given): usable with no device
+extern "C" int hpe_res_fit_multi_instance_words(const int32_t* words, int64_t n_words) {
+  if (!words || n_words < H_WORDS || words[H_MAGIC] != HPE_MAGIC || words[H_KIND] != KIND_RES) return -1;
+  const int64_t oo = words[H_OPS_OFF];
+  if (words[H_NOPS] < 1 || oo < H_WORDS || oo + O_WORDS > n_words) return -1;
+  const int64_t lt = words[oo + O_AUX0], L = words[oo + O_AUX1];
+  if (lt < 0 || L < 1 || lt + L * RL_WORDS > n_words) return -1;
+  return res_fit_instance(words);
+}
+
+extern "C" int hpe_res_fit_multi_instance(const hpe_program* p) {
+  if (!p) return -1;
+  const int* w = hpe_prog_words(p);
+  return w[H_KIND] == KIND_RES ? res_fit_instance(w) : -1;
+}
+
+extern "C" size_t hpe_res_fit_multi_table_size(int32_t n_trials) { return res_fit_table_bytes(n_trials); }
+
+extern "C" int hpe_res_fit_epoch_multi(const hpe_fit_trial* trials, int32_t n_trials, void* table, void* stream) {
+  if (!trials || !table || n_trials < 1) return hpe_fail(HPE_EINVAL, "hpe_res_fit_epoch_multi: null argument");
+  int inst = -1;
+  for (int i = 0; i < n_trials; ++i) {
+    if (const int rc = fit_check_trial(trials[i], "hpe_res_fit_epoch_multi")) return rc;
+    const int id = hpe_res_fit_multi_instance(trials[i].prog);
+    if (id < 0)
+      return hpe_fail(HPE_EINVAL, "hpe_res_fit_epoch_multi: trial %d: not a residual-stack training program "
+                                  "(hpe_fit_epoch_multi runs the create_model family)", i);
+    if (trials[i].stats_stride < 3)
+      return hpe_fail(HPE_EINVAL, "hpe_res_fit_epoch_multi: trial %d: stats_stride %d < 3", i, trials[i].stats_stride);
+    if (i == 0) inst = id;
+    if (id != inst)
+      return hpe_fail(HPE_EINVAL, "hpe_res_fit_epoch_multi: trial %d: kernel instance %d differs from trial 0's %d "
+                                  "(hpe_res_fit_multi_instance: one launch, one instance)", i, id, inst);
+  }
+  return res_fit_multi_launch(trials, n_trials, table, (hipStream_t)stream);
 }

@@ -28,6 +28,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <vector>
+
 #include "../../include/hpe.h"
 #include "hpe_common.h"
 #include "hpe_dev.h"
@@ -48,11 +50,12 @@ static_assert(RES_LDS_BYTES <= 160 * 1024, "res LDS");
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-// -DRES_STAMPS: per-phase s_memtime cycle sums of thread 0, printed at the end of the fit kernel
+// -DRES_STAMPS: per-phase s_memtime cycle sums of thread 0 of block 0 (the only block of the solo
+// entry; under the multi-trial entry one trial of the launch), printed at the end of the fit kernel
 #ifdef RES_STAMPS
 __device__ uint64_t g_rst[10];
 __device__ uint64_t g_rprev;
-#define RSTAMP(i) do { if (threadIdx.x == 0) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); g_rst[i] += t_ - g_rprev; g_rprev = t_; } } while (0)
+#define RSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); g_rst[i] += t_ - g_rprev; g_rprev = t_; } } while (0)
 #else
 #define RSTAMP(i) do {} while (0)
 #endif
@@ -77,11 +80,31 @@ struct ResState {
   float sse, sae;
 };
 
+// Pointers the kernels read their data through.  A kernel argument is known to point to global
+// memory (global loads: SGPR base + 32-bit VGPR offset); a pointer read from memory, as a trial's
+// arguments are under the multi-trial entry, is a generic one to the compiler (flat loads, a 64-bit
+// VGPR address each, which cost the flagship instance 250 B of scratch per lane), and a cast to the
+// global address space and back is folded away.  So that entry's pointers are typed global
+// (ResP<true>), and the code below takes its pointer types as template parameters.
+#define RES_GLOBAL __attribute__((address_space(1)))
+template <bool G>
+struct ResP {
+  template <typename T> using ptr = T*;
+};
+template <>
+struct ResP<true> {
+  template <typename T> using ptr = RES_GLOBAL T*;
+};
+typedef float res_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ res_f2 res_ld2(const float* p) { return *(const res_f2*)p; }
+__device__ __forceinline__ res_f2 res_ld2(RES_GLOBAL const float* p) { return *(RES_GLOBAL const res_f2*)p; }
+
 // which rows a launch trains on: hpe_train_step rows (image = R / P, gathered by idx) or a
 // whole-epoch step's batch (P = 1, rows perm[base + R])
-struct RowMap {
-  const int* idx;
-  const int* perm;
+template <typename IP>
+struct RowMapT {
+  IP idx;
+  IP perm;
   int64_t base, nrows, img_off;
   int P;
   bool fit;
@@ -97,6 +120,7 @@ struct RowMap {
   }
   __device__ __forceinline__ uint64_t dimg(int64_t R) const { return fit ? (uint64_t)R : (uint64_t)(R / P + img_off); }
 };
+typedef RowMapT<const int*> RowMap;
 
 // the layer activations on the hot path: softsign in a few VALU ops (reciprocal approximation,
 // ~1 ulp relative), tanh as tanhf (these kernels are exact-fp32: hpe_dev.h fast_tanh5's absolute
@@ -153,13 +177,13 @@ __host__ __device__ constexpr int res_canon_wo(int l) {
   return o;
 }
 
-template <int KS, int NB, bool BOTL, int HA>
-__device__ __forceinline__ ResDesc<KS, NB, BOTL> res_desc(const int* lt, int post) {
+template <int KS, int NB, bool BOTL, int HA, typename LP>
+__device__ __forceinline__ ResDesc<KS, NB, BOTL> res_desc(LP lt, int post) {
   using G = ResGeo<KS, NB, BOTL>;
   ResDesc<KS, NB, BOTL> D;
 #pragma unroll
   for (int l = 0; l < G::NLAY; ++l) {
-    const int* e = lt + l * RL_WORDS;
+    const LP e = lt + l * RL_WORDS;
     LD& d = D.l[l];
     if (HA >= 0) {
       d.K = res_canon_k<KS, NB, BOTL>(l);
@@ -270,11 +294,10 @@ __device__ __forceinline__ void res_dw16(f4& acc, float& dbp, f4 a_r, f4 dz_r, f
 }
 
 // forward + loss + backward of one 16-row block starting at batch row R0
-template <int KS, int NB, bool BOTL>
+template <int KS, int NB, bool BOTL, typename XP, typename RM>
 __device__ __forceinline__ void res_block(ResState<KS, NB, BOTL>& S, const ResDesc<KS, NB, BOTL>& D,
-                                          const float* prm, const float* __restrict__ x,
-                                          const float* __restrict__ ytrue, const RowMap& rm, int64_t R0,
-                                          uint64_t seed, float inv_count, float* scr, int g, int c) {
+                                          const float* prm, XP __restrict__ x, XP __restrict__ ytrue, const RM& rm,
+                                          int64_t R0, uint64_t seed, float inv_count, float* scr, int g, int c) {
   using G = ResGeo<KS, NB, BOTL>;
   constexpr int CIN = G::CIN;
   const int64_t Rc = R0 + c;
@@ -288,11 +311,11 @@ __device__ __forceinline__ void res_block(ResState<KS, NB, BOTL>& S, const ResDe
   f4 a0, y0;
   uint32_t m0;
   {
-    const float* xp = x + rm.src(Rl) * CIN + KS * g;
+    const XP xp = x + rm.src(Rl) * CIN + KS * g;
     float xr[KS];
 #pragma unroll
     for (int s = 0; s < KS; s += 2) {
-      const float2 v = *(const float2*)(xp + s);
+      const res_f2 v = res_ld2(xp + s);
       xr[s] = v.x;
       xr[s + 1] = v.y;
     }
@@ -309,7 +332,7 @@ __device__ __forceinline__ void res_block(ResState<KS, NB, BOTL>& S, const ResDe
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const int64_t R = min(R0 + 4 * g + s, rm.nrows - 1);
-    const float* xp = x + rm.src(R) * CIN;
+    const XP xp = x + rm.src(R) * CIN;
 #pragma unroll
     for (int b = 0; b < G::NXB; ++b) {
       const int ch = 16 * b + c;
@@ -344,7 +367,7 @@ __device__ __forceinline__ void res_block(ResState<KS, NB, BOTL>& S, const ResDe
   // ---- MSE: lanes g = 0 hold the row's 3 outputs
   f4 dout = {0.f, 0.f, 0.f, 0.f};
   if (g == 0 && valid) {
-    const float* yl = ytrue + rm.label(Rl) * 3;
+    const XP yl = ytrue + rm.label(Rl) * 3;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const float err = out[i] - yl[i];
@@ -499,32 +522,39 @@ __global__ void __launch_bounds__(RES_NW * 64) res_train_kernel(Args a) {
 }
 
 // ---- hpe_fit_epoch: the whole epoch in one workgroup ------------------------------------------------
-struct ResFitArgs {
-  const int* prog;
-  float* params;
-  float* params_t;
-  float* m;
-  float* v;
-  const float* l2;
-  const int* tpos;
-  const float* x;
-  const float* ytrue;
-  const int* perm;
+// G: an entry of the multi-trial table (pointers typed global, see ResP); the layout is the same
+template <bool G>
+struct ResFitArgsT {
+  template <typename T> using P = typename ResP<G>::template ptr<T>;
+  P<const int> prog;
+  P<float> params;
+  P<float> params_t;
+  P<float> m;
+  P<float> v;
+  P<const float> l2;
+  P<const int> tpos;
+  P<const float> x;
+  P<const float> ytrue;
+  P<const int> perm;
   int n, bs, steps, kind;
   float b1, b2, eps;
-  const float* alpha;       // [steps] step sizes (lr for SGD), host-computed as hpe_optim_step
+  P<const float> alpha;     // [steps] step sizes (lr for SGD), host-computed as hpe_optim_step
   uint64_t seed_base;       // dropout seed of step s = seed_base + iter0 + 1 + s
   int64_t iter0;
-  float* stats;             // [steps][stats_stride]: sse, sae, regularisation loss
+  P<float> stats;           // [steps][stats_stride]: sse, sae, regularisation loss
   int stats_stride;
-  int* flags;               // workspace word 1 (always 0: exact fp32 throughout)
+  P<int> flags;             // workspace word 1 (always 0: exact fp32 throughout)
 };
+typedef ResFitArgsT<false> ResFitArgs;
+typedef ResFitArgsT<true> ResFitEnt;
+static_assert(sizeof(ResFitEnt) == sizeof(ResFitArgs), "a table entry is a ResFitArgs");
 
 // one step of the Keras legacy optimizer over the workgroup's parameters in LDS from the summed
 // flat gradient copies (hpe_rowprog.hip optim_update with gscale 1: the same float operations), the
 // regularisation loss on the pre-update weights, and the step's stats row
-__device__ __forceinline__ float res_opt_one(const ResFitArgs& a, float alpha, float wi, float c2, float g,
-                                             float& mi, float& vi) {
+template <typename A>
+__device__ __forceinline__ float res_opt_one(const A& a, float alpha, float wi, float c2, float g, float& mi,
+                                             float& vi) {
   const float gr = fmaf(g, 1.f, 2.f * c2 * wi);
   if (a.kind == HPE_OPT_SGD) return wi - alpha * gr;
   if (a.kind == HPE_OPT_ADAM) {
@@ -537,7 +567,8 @@ __device__ __forceinline__ float res_opt_one(const ResFitArgs& a, float alpha, f
   return wi - alpha * (mi / (vi + a.eps));
 }
 
-__device__ __forceinline__ void res_opt_step(const ResFitArgs& a, float* prm, float* mom, float* vel, const float* cp,
+template <typename A>
+__device__ __forceinline__ void res_opt_step(const A& a, float* prm, float* mom, float* vel, const float* cp,
                                              int stride, int npt, int s, float* misc, int tid, int lane, int wave) {
   const float alpha = a.alpha[s];
   float reg = 0.f;
@@ -557,19 +588,31 @@ __device__ __forceinline__ void res_opt_step(const ResFitArgs& a, float* prm, fl
   const float sse = res_sum4(cp, stride, npt), sae = res_sum4(cp, stride, npt + 1);
   __syncthreads();
   if (tid == 0) {
-    float* st = a.stats + (size_t)s * a.stats_stride;
+    const auto st = a.stats + (size_t)s * a.stats_stride;
     st[0] = sse;
     st[1] = sae;
     st[2] = ((misc[0] + misc[1]) + (misc[2] + misc[3])) + ((misc[4] + misc[5]) + (misc[6] + misc[7]));
   }
 }
 
-template <int KS, int NB, bool BOTL, int HA>
-__global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs a) {
+template <bool MULTI>
+__device__ __forceinline__ ResFitArgsT<MULTI> res_trial(const ResFitArgs& solo, const ResFitEnt* __restrict__ table) {
+  if constexpr (MULTI) return table[blockIdx.x];   // a wave-uniform address: scalar loads into SGPRs
+  else return solo;
+}
+
+// One kernel body, two entries (as csrc/hpe_fit.hip fit_kernel): !MULTI is the one-workgroup launch
+// of hpe_fit_epoch with its trial in `solo` (table unused); MULTI is a grid of independent trials,
+// block b taking its arguments from table[b].  Everything below the entry works from `a` alone and
+// in the workgroup's own LDS, so nothing crosses trials and no block waits for another: a grid
+// larger than the card holds at once runs in rounds.
+template <int KS, int NB, bool BOTL, int HA, bool MULTI>
+__global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs solo, const ResFitEnt* __restrict__ table) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int* prog = a.prog;
-  const int* o = prog + prog[H_OPS_OFF];
-  const int* lt = prog + o[O_AUX0];
+  const ResFitArgsT<MULTI> a = res_trial<MULTI>(solo, table);
+  const auto prog = a.prog;
+  const auto o = prog + prog[H_OPS_OFF];
+  const auto lt = prog + o[O_AUX0];
   const int npt = prog[H_NPARAMS_TRAIN];
   const int stride = (npt + 4 + 3) & ~3;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -591,7 +634,7 @@ __global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs a) {
   __syncthreads();
   ResState<KS, NB, BOTL> S;
 #ifdef RES_STAMPS
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
     for (int i = 0; i < 10; ++i) g_rst[i] = 0;
     g_rprev = __builtin_amdgcn_s_memtime();
   }
@@ -600,7 +643,7 @@ __global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs a) {
     const int64_t base = (int64_t)s * a.bs;
     const int nb = (int)min((int64_t)a.bs, (int64_t)a.n - base);
     res_zero(S);
-    RowMap rm = {nullptr, a.perm, base, nb, 0, 1, true};
+    RowMapT<decltype(a.perm)> rm = {nullptr, a.perm, base, nb, 0, 1, true};
     const uint64_t seed = a.seed_base + (uint64_t)(a.iter0 + 1 + s);
     const float inv = 1.f / (float)(nb * 3);
     const int nblk = (nb + RES_T - 1) / RES_T;
@@ -612,7 +655,7 @@ __global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs a) {
     RSTAMP(5);
   }
 #ifdef RES_STAMPS
-  if (threadIdx.x == 0)
+  if (threadIdx.x == 0 && blockIdx.x == 0)
     printf("RSTAMP steps %d: fwd0 %llu fwd %llu bwd %llu dw0 %llu reduce %llu opt %llu\n", a.steps,
            (unsigned long long)g_rst[0], (unsigned long long)g_rst[1], (unsigned long long)g_rst[2],
            (unsigned long long)g_rst[3], (unsigned long long)g_rst[4], (unsigned long long)g_rst[5]);
@@ -631,35 +674,44 @@ __global__ void __launch_bounds__(RES_NW * 64) res_fit_kernel(ResFitArgs a) {
 
 // ---- host side ----------------------------------------------------------------------------------
 typedef void (*res_train_fn)(Args);
-typedef void (*res_fit_fn)(ResFitArgs);
+typedef void (*res_fit_fn)(ResFitArgs, const ResFitEnt*);
+// one kernel instance <KS, NB, BOTL, HA>: the per-step kernel and the epoch kernel's two entries
+struct ResFns {
+  res_train_fn train;
+  res_fit_fn fit, fit_multi;
+};
 
 #ifndef RES_FAST
 #define RES_FAST 0
 #endif
 #define RES_HA (RES_FAST ? ACT_SOFTSIGN : -1)
 #if RES_PART != 0
+template <int KS, int NB, bool BOTL>
+static ResFns res_fns_of() {
+  return {res_train_kernel<KS, NB, BOTL, RES_HA>, res_fit_kernel<KS, NB, BOTL, RES_HA, false>,
+          res_fit_kernel<KS, NB, BOTL, RES_HA, true>};
+}
 template <int KS, bool BOTL>
-static void res_pick_nb(int nb, res_train_fn* t, res_fit_fn* f) {
+static ResFns res_pick_nb(int nb) {
   switch (nb) {
-    case 1: *t = res_train_kernel<KS, 1, BOTL, RES_HA>; *f = res_fit_kernel<KS, 1, BOTL, RES_HA>; break;
-    case 2: *t = res_train_kernel<KS, 2, BOTL, RES_HA>; *f = res_fit_kernel<KS, 2, BOTL, RES_HA>; break;
-    case 3: *t = res_train_kernel<KS, 3, BOTL, RES_HA>; *f = res_fit_kernel<KS, 3, BOTL, RES_HA>; break;
-    case 4: *t = res_train_kernel<KS, 4, BOTL, RES_HA>; *f = res_fit_kernel<KS, 4, BOTL, RES_HA>; break;
-    default: break;
+    case 1: return res_fns_of<KS, 1, BOTL>();
+    case 2: return res_fns_of<KS, 2, BOTL>();
+    case 3: return res_fns_of<KS, 3, BOTL>();
+    case 4: return res_fns_of<KS, 4, BOTL>();
+    default: return {nullptr, nullptr, nullptr};
   }
 }
 #define RES_FNS_NAME3(n, f) res_fns_##n##_##f
 #define RES_FNS_NAME(n, f) RES_FNS_NAME3(n, f)
 // a residual stack of nb blocks (bot: with the bottleneck)
-void RES_FNS_NAME(RES_PART, RES_FAST)(int nb, bool bot, res_train_fn* t, res_fit_fn* f) {
-  if (bot) res_pick_nb<RES_PART / 4, true>(nb, t, f);
-  else res_pick_nb<RES_PART / 4, false>(nb, t, f);
+ResFns RES_FNS_NAME(RES_PART, RES_FAST)(int nb, bool bot) {
+  return bot ? res_pick_nb<RES_PART / 4, true>(nb) : res_pick_nb<RES_PART / 4, false>(nb);
 }
 #else
-void res_fns_88_0(int nb, bool bot, res_train_fn* t, res_fit_fn* f);
-void res_fns_88_1(int nb, bool bot, res_train_fn* t, res_fit_fn* f);
-void res_fns_96_0(int nb, bool bot, res_train_fn* t, res_fit_fn* f);
-void res_fns_96_1(int nb, bool bot, res_train_fn* t, res_fit_fn* f);
+ResFns res_fns_88_0(int nb, bool bot);
+ResFns res_fns_88_1(int nb, bool bot);
+ResFns res_fns_96_0(int nb, bool bot);
+ResFns res_fns_96_1(int nb, bool bot);
 
 // the compile-time-activation kernels: every hidden dense softsign, the post-add activation relu,
 // the output linear (create_model_complex, Model-88/attention_model.py:97-169)
@@ -680,31 +732,30 @@ static bool res_fast(const int* w) {
   return off == w[H_NPARAMS_TRAIN];
 }
 
-static bool res_pick(const int* w, res_train_fn* t, res_fit_fn* f) {
-  *t = nullptr;
-  *f = nullptr;
+// the kernels of a residual-stack program and (id) which instance they are: input width, block
+// count, bottleneck, compile-time against runtime activations; train == nullptr when there is none
+static ResFns res_pick(const int* w, int* id = nullptr) {
+  const ResFns none = {nullptr, nullptr, nullptr};
   const int* o = w + w[H_OPS_OFF];
-  if (o[O_TYPE] != OP_RES) return false;
+  if (o[O_TYPE] != OP_RES) return none;
   const int cin = o[O_K], nb = o[O_AUX3], F = o[O_N];
   const bool bot = o[O_FLAGS] > 0;
-  if (nb <= 0 || F != 16 || o[O_AUX1] != 2 * nb + 2 + (bot ? 1 : 0)) return false;
+  if (nb <= 0 || F != 16 || o[O_AUX1] != 2 * nb + 2 + (bot ? 1 : 0)) return none;
   const bool fast = res_fast(w);
-  if (cin == 88) (fast ? res_fns_88_1 : res_fns_88_0)(nb, bot, t, f);
-  else if (cin == 96) (fast ? res_fns_96_1 : res_fns_96_0)(nb, bot, t, f);
-  return *t != nullptr;
+  if (id) *id = (((cin == 96 ? 1 : 0) * 2 + (fast ? 1 : 0)) * 4 + (nb - 1)) * 2 + (bot ? 1 : 0);
+  if (cin == 88) return (fast ? res_fns_88_1 : res_fns_88_0)(nb, bot);
+  if (cin == 96) return (fast ? res_fns_96_1 : res_fns_96_0)(nb, bot);
+  return none;
 }
 int res_supported(const int* w) {
-  res_train_fn t;
-  res_fit_fn f;
-  return w[H_MODE] == MODE_TRAIN && w[H_NPARAMS_TRAIN] <= RES_MAXP && res_pick(w, &t, &f) ? 1 : 0;
+  return w[H_MODE] == MODE_TRAIN && w[H_NPARAMS_TRAIN] <= RES_MAXP && res_pick(w).train ? 1 : 0;
 }
 
 int res_grid_cap(int n_cu) { return n_cu; }
 
 int res_launch(const int* w, const Args& a, int grid, hipStream_t s) {
-  res_train_fn t;
-  res_fit_fn f;
-  if (!res_pick(w, &t, &f)) return 2;
+  const res_train_fn t = res_pick(w).train;
+  if (!t) return 2;
   const int lds = RES_LDS_BYTES;
   hipFuncSetAttribute((const void*)t, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const int tv = hpe_tev_begin(s);
@@ -713,28 +764,62 @@ int res_launch(const int* w, const Args& a, int grid, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
-int res_fit_launch(const int* w, const int* dwords, float* params, float* params_t, float* m, float* v,
-                   const float* l2, const int32_t* tpos, const float* x, const float* y_true, const int32_t* perm,
-                   int64_t n, int32_t batch, int32_t kind, float beta_1, float beta_2, float epsilon,
-                   const float* alpha, uint64_t seed_base, int64_t iter0, float* stats, int32_t stats_stride,
-                   void* workspace, hipStream_t s) {
-  res_train_fn t;
-  res_fit_fn f;
-  if (!res_pick(w, &t, &f)) return 2;
+// the epoch kernel's arguments of one (checked, KIND_RES) trial
+static ResFitArgs res_fit_args(const hpe_fit_trial& t) {
   ResFitArgs a = {};
-  a.prog = dwords;
-  a.params = params; a.params_t = params_t; a.m = m; a.v = v; a.l2 = l2; a.tpos = tpos;
-  a.x = x; a.ytrue = y_true; a.perm = perm;
-  a.n = (int)n; a.bs = batch; a.steps = (int)((n + batch - 1) / batch); a.kind = kind;
-  a.b1 = beta_1; a.b2 = beta_2; a.eps = epsilon;
-  a.alpha = alpha; a.seed_base = seed_base; a.iter0 = iter0;
-  a.stats = stats; a.stats_stride = stats_stride;
-  a.flags = (int*)workspace;
+  a.prog = hpe_prog_dwords(t.prog);
+  a.params = t.params; a.params_t = t.params_t; a.m = t.m; a.v = t.v; a.l2 = t.l2; a.tpos = t.tpos;
+  a.x = t.x; a.ytrue = t.y_true; a.perm = t.perm;
+  a.n = (int)t.n; a.bs = t.batch; a.steps = (int)((t.n + t.batch - 1) / t.batch); a.kind = t.kind;
+  a.b1 = t.beta_1; a.b2 = t.beta_2; a.eps = t.epsilon;
+  a.alpha = t.alpha; a.seed_base = t.seed_base; a.iter0 = t.iter0;
+  a.stats = t.stats; a.stats_stride = t.stats_stride;
+  a.flags = (int*)t.workspace;
+  return a;
+}
+
+int res_fit_launch(const hpe_fit_trial& t, hipStream_t s) {
+  const res_fit_fn f = res_pick(hpe_prog_words(t.prog)).fit;
+  if (!f) return 2;
+  const ResFitArgs a = res_fit_args(t);
   const int lds = RES_LDS_BYTES;
   hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const int tv = hpe_tev_begin(s);
-  hipLaunchKernelGGL(f, dim3(1), dim3(RES_NW * 64), lds, s, a);
+  hipLaunchKernelGGL(f, dim3(1), dim3(RES_NW * 64), lds, s, a, (const ResFitEnt*)nullptr);
   hpe_tev_end(s, tv);
   return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// ---- several residual-stack trials in one launch: block b trains trial b -------------------------
+int res_fit_instance(const int* w) {
+  int id = -1;
+  if (w[H_KIND] != KIND_RES || !res_supported(w) || !res_pick(w, &id).fit_multi) return -1;
+  return id;
+}
+
+size_t res_fit_table_bytes(int n_trials) { return n_trials < 1 ? 0 : (size_t)n_trials * sizeof(ResFitArgs); }
+
+// trials: checked, KIND_RES, one shared instance (hpe_res_fit_epoch_multi); HPE_OK or hpe_fail's code
+int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s) {
+  const res_fit_fn f = res_pick(hpe_prog_words(trials[0].prog)).fit_multi;
+  if (!f) return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: no kernel");
+  std::vector<ResFitArgs> host(n_trials);
+  for (int i = 0; i < n_trials; ++i) host[i] = res_fit_args(trials[i]);
+  // the staging vector dies on return, so the copy is complete before it does: ordered on the
+  // stream after whatever still reads the table, then waited for
+  if (hipMemcpyAsync(table, host.data(), res_fit_table_bytes(n_trials), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: table copy: %s", hipGetErrorString(hipGetLastError()));
+  for (int i = 0; i < n_trials; ++i)  // the flags word, as hpe_fit_epoch
+    if (hipMemsetAsync(trials[i].workspace, 0, 64, s) != hipSuccess)
+      return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: memset: %s", hipGetErrorString(hipGetLastError()));
+  const int lds = RES_LDS_BYTES;
+  if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+    return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
+  const int tv = hpe_tev_begin(s);
+  hipLaunchKernelGGL(f, dim3(n_trials), dim3(RES_NW * 64), lds, s, ResFitArgs{}, (const ResFitEnt*)table);
+  hpe_tev_end(s, tv);
+  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: launch failed");
+  return HPE_OK;
 }
 #endif

@@ -42,6 +42,10 @@ SIGNATURES = {
     'hpe_fit_multi_table_size': (_sz, [_i32]),
     'hpe_fit_multi_supported': (ctypes.c_int, [_vp, _i32]),
     'hpe_fit_epoch_multi': (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    'hpe_res_fit_multi_instance': (ctypes.c_int, [_vp]),
+    'hpe_res_fit_multi_instance_words': (ctypes.c_int, [_vp, _i64]),
+    'hpe_res_fit_multi_table_size': (_sz, [_i32]),
+    'hpe_res_fit_epoch_multi': (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     'hpe_blazeface_create': (ctypes.c_int, [_vp, _i64, ctypes.POINTER(_vp)]),
     'hpe_blazeface_destroy': (ctypes.c_int, [_vp]),
     'hpe_blazeface_workspace_size': (_sz, [_vp, _i64]),

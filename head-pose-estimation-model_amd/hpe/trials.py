@@ -10,6 +10,11 @@ workgroups running exactly the arithmetic of a solo launch, so every model ends 
 on the fused path.  Per epoch the host groups the active trials by kernel instance, splits each group
 into launches (hpe_fit_multi_plan), uploads all permutations and step sizes in one transfer and
 reads every trial's flags, statistics and validation sums back in one.
+
+Residual stacks (create_model_complex and the stacks like it, csrc/hpe_res.hip) train with one
+workgroup for the whole epoch; with residual_stacks=True they are trials too, block b of one
+hpe_res_fit_epoch_multi launch per kernel instance training trial b, beside the create_model-family
+launches of the same call.
 """
 import ctypes
 import math
@@ -30,6 +35,7 @@ class _Trial:
     def __init__(self, i, model, bs, seed, callbacks, n):
         self.i, self.model, self.bs, self.seed = i, model, bs, int(seed)
         self.eng = model._eng()
+        self.res = self.eng.program('train', 1).prog.kind == 'res'   # one workgroup per trial, never flags
         self.steps = math.ceil(n / bs)
         self.nbs = [min(n, (s + 1) * bs) - s * bs for s in range(self.steps)]
         self.rng = np.random.RandomState(self.seed)       # Model.fit's shuffle stream
@@ -46,7 +52,7 @@ def _refuse(i, why):
     raise ValueError('fit_many: model %d: %s' % (i, why))
 
 
-def _check(models, batch_sizes, C, P):
+def _check(models, batch_sizes, C, P, residual_stacks=False):
     """Everything fit_many refuses, before any model is trained."""
     env = os.environ.get('HPE_FIT_FUSED')
     for i, (m, bs) in enumerate(zip(models, batch_sizes)):
@@ -65,14 +71,16 @@ def _check(models, batch_sizes, C, P):
     for i, (m, bs) in enumerate(zip(models, batch_sizes)):
         eng = m._eng()
         c = eng.program('train', 1)
-        if c.prog.kind == 'res':
+        res = c.prog.kind == 'res'
+        if res and not residual_stacks:
             _refuse(i, 'residual-stack programs run one per launch (Model.fit)')
         if bs > eng.FIT_FUSED_AUTO_MAX and env != '1':
             _refuse(i, 'batch %d is above %d: set HPE_FIT_FUSED=1 to train it on the fused path'
                     % (bs, eng.FIT_FUSED_AUTO_MAX))
         if getattr(eng, '_fit_disabled', False):
             _refuse(i, 'an earlier epoch launch of this model timed out (fused path disabled)')
-        if c.prog.kind != 'mlp2' or lib.hpe_fit_supported(c.h, int(bs)) != 1 or lib.hpe_fit_multi_instance(c.h) < 0:
+        inst = lib.hpe_res_fit_multi_instance(c.h) if res else lib.hpe_fit_multi_instance(c.h)
+        if c.prog.kind not in ('mlp2', 'res') or lib.hpe_fit_supported(c.h, int(bs)) != 1 or inst < 0:
             _refuse(i, 'the epoch launch does not support this program at batch %d (hpe_fit_supported)' % bs)
 
 
@@ -94,34 +102,53 @@ def plan_launches(groups, lane_cap):
 
 
 def _launch(trials, exact, tables, record):
-    """One epoch of `trials` (fused): grouped by kernel instance, split into launches."""
+    """One epoch of `trials` (fused): grouped by kernel instance, split into launches.  The
+    create_model family goes through hpe_fit_multi_plan and hpe_fit_epoch_multi; residual stacks
+    need no plan (a trial is one workgroup that waits for no other): one hpe_res_fit_epoch_multi
+    launch per instance, whatever the number of trials."""
     import torch
     lib = _lib.load()
+
+    def table(need, dev):
+        slot = len(record)
+        if slot >= len(tables) or tables[slot].numel() < need:
+            tables[slot:slot + 1] = [torch.empty(need, dtype=torch.uint8, device=dev)]
+        return _lib.ptr(tables[slot])
+
     by_inst = {}
     for t in trials:
-        by_inst.setdefault(lib.hpe_fit_multi_instance(t.eng.program('train', 1).h), []).append(t)
-    for inst in sorted(by_inst):
-        ts = by_inst[inst]
+        h = t.eng.program('train', 1).h
+        key = (1, lib.hpe_res_fit_multi_instance(h)) if t.res else (0, lib.hpe_fit_multi_instance(h))
+        by_inst.setdefault(key, []).append(t)
+    for res, inst in sorted(by_inst):
+        ts = by_inst[res, inst]
+        dev = ts[0].eng.device
+        if res:
+            arr = (_lib.FitTrial * len(ts))(*[t.ft for t in ts])
+            tab = table(lib.hpe_res_fit_multi_table_size(len(ts)), dev)
+            _lib.check(lib.hpe_res_fit_epoch_multi(arr, len(ts), tab, _lib.stream()), 'hpe_res_fit_epoch_multi')
+            record.append([t.i for t in ts])
+            continue
         cap = lib.hpe_fit_multi_lane_cap(ts[0].eng.program('train', 1).h)
         for idxs in plan_launches([t.eng.fit_groups() for t in ts], cap):
             arr = (_lib.FitTrial * len(idxs))(*[ts[j].ft for j in idxs])
-            need = lib.hpe_fit_multi_table_size(len(idxs))
-            slot = len(record)
-            if slot >= len(tables) or tables[slot].numel() < need:
-                tab = torch.empty(need, dtype=torch.uint8, device=ts[0].eng.device)
-                tables[slot:slot + 1] = [tab]
-            _lib.check(lib.hpe_fit_epoch_multi(arr, len(idxs), int(exact), _lib.ptr(tables[slot]), _lib.stream()),
-                       'hpe_fit_epoch_multi')
+            tab = table(lib.hpe_fit_multi_table_size(len(idxs)), dev)
+            _lib.check(lib.hpe_fit_epoch_multi(arr, len(idxs), int(exact), tab, _lib.stream()), 'hpe_fit_epoch_multi')
             record.append([ts[j].i for j in idxs])
 
 
 def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=None, callbacks=None,
-             shuffle=True, initial_epoch=0, verbose=0):
+             shuffle=True, initial_epoch=0, verbose=0, residual_stacks=False):
     """Train `models` (compiled hpe.Models, each with its own weights, optimizer, dropout and L2;
     widths may differ) on the shared x / y, several per epoch launch.  batch_size: an int or one per
     model; seeds: one per model (default hpe.random.seed() + i); callbacks: None or one list per
     model.  Returns one History per model; model i ends exactly as after hpe.set_seed(seeds[i]) and
     models[i].fit(...) alone on the fused path.  The global seed state is left as it was.
+    residual_stacks=True also accepts residual-stack models (create_model_complex and the stacks
+    like it): each is one workgroup of an hpe_res_fit_epoch_multi launch, one launch per kernel
+    instance, and a call may mix them with the create_model family.  The default stays False, which
+    refuses them by name as before this keyword existed: that refusal is part of the tested
+    behaviour, and making True the default is a change of its own.
     fit_many.last_plan records, per epoch, the launches made (lists of model indices), every
     trial's flags word and the trials re-run on the exact-fp32 path."""
     import torch
@@ -136,7 +163,7 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
         raise ValueError('fit_many: batch_size, seeds and callbacks need one entry per model (%d)' % T)
     rows, n, P, _ = models[0]._rows(x)
     lab = models[0]._labels(y, n)
-    _check(models, bss, rows.shape[1], P)
+    _check(models, bss, rows.shape[1], P, residual_stacks)
     if validation_data is not None:
         vrows, vn, vP, _ = models[0]._rows(validation_data[0])
         vlab = models[0]._labels(validation_data[1], vn)
@@ -191,7 +218,8 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
         fused = [t for t in act if t.fused]
         for t in fused:
             t.ft = t.eng.fit_trial(t.model.optimizer, xd, yd, t.idx, t.bs, t.stats, t.seed_base, t.alpha)
-            t.saved = [s.clone() for s in t.eng.fit_state()]
+            # what a flagged epoch restores; a residual stack never flags (exact fp32, no exchange)
+            t.saved = None if t.res else [s.clone() for s in t.eng.fit_state()]
         record = []
         _launch(fused, 0, tables, record)
         for t in act:
@@ -220,6 +248,8 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
 
         res = read_back(act)
         flags = {t.i: res[t.i][0] for t in act}
+        for t in fused:
+            assert not (t.res and flags[t.i]), 'residual-stack trial %d set flags %d' % (t.i, flags[t.i])
         redo = [t for t in fused if res[t.i][0]]
         exact = [t for t in redo if res[t.i][0] & 1 and not res[t.i][0] & 2]
         if exact:   # fp16 range exceeded: these trials redo the epoch exactly, together

@@ -241,6 +241,37 @@ int hpe_fit_epoch_multi(const hpe_fit_trial *trials, int32_t n_trials, int32_t e
                         void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Several residual stacks (programs of kind res: create_model_complex and the stacks like it,
+ * csrc/hpe_res.hip) in ONE epoch launch.  hpe_fit_epoch trains such a program with one workgroup for
+ * the whole epoch; here block b of a grid of n_trials workgroups trains trials[b], with the same
+ * arithmetic (bit-identical results).  A trial is one workgroup that talks to no other, so there is
+ * no placement plan and no residency cap: blocks beyond what the card holds at once simply wait for
+ * a CU.  Nothing crosses trials: each has its own program (dropout rates, layer table), parameters,
+ * optimizer state and kind, L2 vector, permutation, step sizes, seeds, stats rows ([sum e^2,
+ * sum |e|, regularisation loss] per step, stats_stride >= 3) and workspace, whose flags word [1] is
+ * always 0 after the launch (every GEMM is exact fp32 and no workgroup waits for another).  There is
+ * no `exact` argument for the same reason.  The existing entry points keep refusing these programs:
+ * hpe_fit_multi_instance returns -1, hpe_fit_multi_lane_cap 0, hpe_fit_epoch_multi HPE_EINVAL.
+ *
+ * hpe_res_fit_multi_instance: an id of prog's kernel instance (input width 88 / 96, number of
+ * residual blocks, with / without the bottleneck, compiled-in softsign / relu against run-time
+ * activations), -1 if prog is NULL or not a supported residual-stack training program; all trials of
+ * one launch must share it.  hpe_res_fit_multi_instance_words: the same id from the word stream
+ * hpe_program_create takes (-1 if it is not a well-formed one).  Both are host arithmetic only and
+ * need no device.
+ * hpe_res_fit_multi_table_size: bytes of device memory for the launch's argument table (0 if
+ * n_trials < 1).
+ * hpe_res_fit_epoch_multi: checks every trial before any device call (hpe_fit_epoch's argument
+ * checks, kind res, stats_stride >= 3, one shared instance; otherwise HPE_EINVAL with a message that
+ * names the trial), zeroes each trial's workspace, writes the table through the stream (the call
+ * waits for that copy; the table must stay untouched until the launch has finished) and makes one
+ * launch of n_trials workgroups. */
+int hpe_res_fit_multi_instance(const hpe_program *prog);
+int hpe_res_fit_multi_instance_words(const int32_t *words, int64_t n_words);
+size_t hpe_res_fit_multi_table_size(int32_t n_trials);
+int hpe_res_fit_epoch_multi(const hpe_fit_trial *trials, int32_t n_trials, void *table, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BlazeFace backbone — replaces the TF call on the fused BlazeFace+regressor
  * graph, `self.model.predict(...)` at BlazePoser/blazeFaceDetectorH5.py:272, for a whole batch.
  * words: the plan hpe/blazeface.py builds from the unified model's model_config (csrc/hpe_prog.h
