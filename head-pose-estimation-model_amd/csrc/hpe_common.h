@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/hpe.h"
 #include "hpe_prog.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -290,18 +291,30 @@ int chain_launch(const int* words_host, const Args& a, int grid, hipStream_t s);
 int res_supported(const int* words);
 int res_grid_cap(int n_cu);
 int res_launch(const int* words_host, const Args& a, int grid, hipStream_t s);
-struct hpe_fit_trial;  // include/hpe.h
-int res_fit_launch(const hpe_fit_trial& t, hipStream_t s);
-// several trials in one launch (block b trains trial b): the kernel-instance id of a program's word
-// stream (-1: none), the bytes of an n-trial argument table, and the launch itself
+// the epoch launch of n_trials trials (block b trains trial b; one trial: the solo entry on a grid of
+// one, table unused), the kernel-instance id of a program's word stream (-1: none) and the bytes of
+// an n-trial argument table.  who: the entry point's name, for messages
 int res_fit_instance(const int* words);
 size_t res_fit_table_bytes(int n_trials);
-int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s);
+int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s, const char* who);
 
 // a program's word stream: host copy (kernel geometry) and device copy (kernel argument)
 struct hpe_program;
 const int* hpe_prog_words(const hpe_program* p);
 const int* hpe_prog_dwords(const hpe_program* p);
+
+// the members the epoch kernels' argument structs share (FitArgs in hpe_fit.hip, ResFitArgsT in
+// hpe_res.hip: prog .. stats_stride), from one trial
+template <typename A>
+static inline void fit_trial_fields(const hpe_fit_trial& t, A* a) {
+  a->prog = hpe_prog_dwords(t.prog);
+  a->params = t.params; a->params_t = t.params_t; a->m = t.m; a->v = t.v; a->l2 = t.l2; a->tpos = t.tpos;
+  a->x = t.x; a->ytrue = t.y_true; a->perm = t.perm;
+  a->n = (int)t.n; a->bs = t.batch; a->steps = (int)((t.n + t.batch - 1) / t.batch); a->kind = t.kind;
+  a->b1 = t.beta_1; a->b2 = t.beta_2; a->eps = t.epsilon;
+  a->alpha = t.alpha; a->seed_base = t.seed_base; a->iter0 = t.iter0;
+  a->stats = t.stats; a->stats_stride = t.stats_stride;
+}
 
 // thread-local error message of the C ABI (hpe_last_error); returns code
 int hpe_fail(int code, const char* fmt, ...);

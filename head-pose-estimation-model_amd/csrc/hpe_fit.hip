@@ -831,6 +831,18 @@ static FitFns fit_pick_fns(const int* w, bool split) {
 }
 static fit_fn fit_pick(const int* w, bool split) { return fit_pick_fns(w, split).solo; }
 
+// workgroups of entry k the current device holds at once (CUs x occupancy); 0 on failure
+static int fit_resident(fit_fn k) {
+  int dev = 0, cus = 0, occ = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, FIT_NW * 64, FIT_LDS_BYTES) != hipSuccess)
+    return 0;
+  return occ * cus;
+}
+
 extern "C" int hpe_fit_supported(const hpe_program* p, int32_t batch) {
   if (!p) return 0;
   const int* w = hpe_prog_words(p);
@@ -850,15 +862,7 @@ extern "C" int hpe_fit_supported(const hpe_program* p, int32_t batch) {
   // capacity (occ per CU x CUs), so every workgroup is dispatched without waiting for another to
   // finish. With 8 XCDs (MI355X) the blockIdx % 8 == 0 workers share one XCD; with another XCD
   // count they do not, the launch-start check sees it and the exchange takes the sc1 path.
-  int dev = 0, cus = 0, occ = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  fit_fn k = fit_pick(w, true);
-  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, FIT_NW * 64, FIT_LDS_BYTES) != hipSuccess)
-    return 0;
-  return occ >= 1 && 8 * G <= occ * cus;
+  return 8 * G <= fit_resident(fit_pick(w, true));
 }
 
 extern "C" size_t hpe_fit_workspace_size(const hpe_program* p, int32_t batch) {
@@ -890,14 +894,7 @@ static int fit_fill_args(const hpe_fit_trial& t, FitArgs* out, int* Gout, const 
   if (t.stats_stride < 2 + 4 * G)
     return hpe_fail(HPE_EINVAL, "%s: stats_stride %d < %d", who, t.stats_stride, 2 + 4 * G);
   FitArgs a = {};
-  a.prog = hpe_prog_dwords(t.prog);
-  a.params = t.params; a.params_t = t.params_t; a.m = t.m; a.v = t.v; a.l2 = t.l2; a.tpos = t.tpos;
-  a.x = t.x; a.ytrue = t.y_true; a.perm = t.perm;
-  a.n = (int)t.n; a.bs = t.batch; a.steps = (int)((t.n + t.batch - 1) / t.batch); a.kind = t.kind;
-  a.b1 = t.beta_1;
-  a.b2 = t.beta_2; a.eps = t.epsilon;
-  a.alpha = t.alpha; a.seed_base = t.seed_base; a.iter0 = t.iter0;
-  a.stats = t.stats; a.stats_stride = t.stats_stride;
+  fit_trial_fields(t, &a);
   a.n_train = w[H_NPARAMS_TRAIN];
   a.n_params = w[H_NPARAMS];
   a.n_mirror = (int64_t)1 << 40;  // the mirror's size is the compiler's; checked >= 0 only
@@ -913,6 +910,9 @@ static int fit_fill_args(const hpe_fit_trial& t, FitArgs* out, int* Gout, const 
   return HPE_OK;
 }
 
+static int fit_launch(const hpe_fit_trial* trials, int n, int exact, void* table, hipStream_t s, const char* who);
+
+// the one-trial case of the launch below
 extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_t, float* m, float* v,
                              const float* l2, const int32_t* tpos, const float* x, const float* y_true,
                              const int32_t* perm, int64_t n, int32_t batch, int32_t kind, float lr, float beta_1,
@@ -922,30 +922,11 @@ extern "C" int hpe_fit_epoch(const hpe_program* p, float* params, float* params_
                            batch, kind,  lr,       beta_1, beta_2,  epsilon, alpha,   seed_base, iter0, stats,
                            stats_stride, workspace};
   if (const int rc = fit_check_trial(t, "hpe_fit_epoch")) return rc;
-  const int* w = hpe_prog_words(p);
-  if (w[H_KIND] == KIND_RES) {
+  if (hpe_prog_words(p)[H_KIND] == KIND_RES) {
     if (stats_stride < 3) return hpe_fail(HPE_EINVAL, "hpe_fit_epoch: stats_stride %d < 3", stats_stride);
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, hpe_fit_workspace_size(p, batch), s) != hipSuccess)
-      return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: memset: %s", hipGetErrorString(hipGetLastError()));
-    if (res_fit_launch(t, s))
-      return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: residual-stack launch failed");
-    return HPE_OK;
+    return res_fit_multi_launch(&t, 1, nullptr, (hipStream_t)stream, "hpe_fit_epoch");
   }
-  FitArgs a;
-  int G = 0;
-  if (const int rc = fit_fill_args(t, &a, &G, "hpe_fit_epoch")) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // flags and granules: no tag of an earlier launch (an exact re-run, or iterations restored from
-  // a checkpoint) can match this launch's
-  if (hipMemsetAsync(workspace, 0, hpe_fit_workspace_size(p, batch), s) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: memset: %s", hipGetErrorString(hipGetLastError()));
-  fit_fn k = fit_pick(w, !exact && !hpe_exact_fp32());
-  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
-  hipLaunchKernelGGL(k, dim3(8 * G), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, a, (const FitEnt*)nullptr, (const int*)nullptr);
-  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch: launch failed");
-  return HPE_OK;
+  return fit_launch(&t, 1, exact, nullptr, (hipStream_t)stream, "hpe_fit_epoch");
 }
 
 // ---- several independent trials in one launch ---------------------------------------------------
@@ -991,16 +972,7 @@ extern "C" size_t hpe_fit_multi_table_size(int32_t n_trials) {
 
 // workgroups per lane that may be resident at once: the launch of 8 * max(lane load) workgroups
 // must fit occupancy x CUs, as in hpe_fit_supported; 0 on failure
-static int fit_multi_cap(fit_fn k) {
-  int dev = 0, cus = 0, occ = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, FIT_NW * 64, FIT_LDS_BYTES) != hipSuccess)
-    return 0;
-  return occ * cus / 8;
-}
+static int fit_multi_cap(fit_fn k) { return fit_resident(k) / 8; }
 
 extern "C" int hpe_fit_multi_lane_cap(const hpe_program* p) {
   if (!p) return 0;
@@ -1054,41 +1026,61 @@ extern "C" int hpe_fit_epoch_multi(const hpe_fit_trial* trials, int32_t n_trials
     if (hpe_prog_words(trials[i].prog)[H_KIND] != KIND_MLP2)
       return hpe_fail(HPE_EINVAL, "hpe_fit_epoch_multi: trial %d: residual-stack programs run alone (hpe_fit_epoch)", i);
   }
-  FitFns fns;
-  std::vector<int32_t> G, lane, first_c;
-  if (!fit_multi_prepare(trials, n_trials, !exact && !hpe_exact_fp32(), &fns, &G, &lane, &first_c))
-    return hpe_fail(HPE_EINVAL, "hpe_fit_epoch_multi: the %d trials do not share one kernel instance (input width, "
-                                "activation class) or do not fit one launch (hpe_fit_multi_plan)", n_trials);
-  int load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, depth = 0;
-  for (int i = 0; i < n_trials; ++i) load[lane[i]] += G[i];
-  for (int l = 0; l < 8; ++l) depth = std::max(depth, load[l]);
-  const int grid = 8 * depth;
-  const size_t map_off = fit_multi_map_off(n_trials), bytes = map_off + (size_t)grid * sizeof(int);
-  if (bytes > hpe_fit_multi_table_size(n_trials)) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: map size");
-  std::vector<unsigned char> host(bytes, 0);
-  FitEnt* ent = (FitEnt*)host.data();
-  int* map = (int*)(host.data() + map_off);
-  for (int b = 0; b < grid; ++b) map[b] = -1;
-  for (int i = 0; i < n_trials; ++i) {
+  return fit_launch(trials, n_trials, exact, table, (hipStream_t)stream, "hpe_fit_epoch_multi");
+}
+
+// The epoch launch of n checked KIND_MLP2 trials, for entry point `who`.  One trial runs the solo
+// entry: its arguments by value on a grid of 8 G, no table written and nothing waited for.  Several
+// run the multi entry over the table and block map written here.
+static int fit_launch(const hpe_fit_trial* trials, int n, int exact, void* table, hipStream_t s, const char* who) {
+  const bool split = !exact && !hpe_exact_fp32();
+  FitFns fns = fit_pick_fns(hpe_prog_words(trials[0].prog), split);
+  FitArgs solo = {};
+  int grid = 0;
+  size_t map_off = 0;
+  if (n == 1) {
     int g = 0;
-    if (const int rc = fit_fill_args(trials[i], &ent[i].a, &g, "hpe_fit_epoch_multi")) return rc;
-    ent[i].G = g;
-    for (int c = 0; c < g; ++c) map[8 * (first_c[i] + c) + lane[i]] = i * 64 + c;
+    if (const int rc = fit_fill_args(trials[0], &solo, &g, who)) return rc;
+    grid = 8 * g;
+  } else {
+    std::vector<int32_t> G, lane, first_c;
+    if (!fit_multi_prepare(trials, n, split, &fns, &G, &lane, &first_c))
+      return hpe_fail(HPE_EINVAL, "%s: the %d trials do not share one kernel instance (input width, "
+                                  "activation class) or do not fit one launch (hpe_fit_multi_plan)", who, n);
+    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, depth = 0;
+    for (int i = 0; i < n; ++i) load[lane[i]] += G[i];
+    for (int l = 0; l < 8; ++l) depth = std::max(depth, load[l]);
+    grid = 8 * depth;
+    map_off = fit_multi_map_off(n);
+    const size_t bytes = map_off + (size_t)grid * sizeof(int);
+    if (bytes > hpe_fit_multi_table_size(n)) return hpe_fail(HPE_ERUNTIME, "%s: map size", who);
+    std::vector<unsigned char> host(bytes, 0);
+    FitEnt* ent = (FitEnt*)host.data();
+    int* map = (int*)(host.data() + map_off);
+    for (int b = 0; b < grid; ++b) map[b] = -1;
+    for (int i = 0; i < n; ++i) {
+      int g = 0;
+      if (const int rc = fit_fill_args(trials[i], &ent[i].a, &g, who)) return rc;
+      ent[i].G = g;
+      for (int c = 0; c < g; ++c) map[8 * (first_c[i] + c) + lane[i]] = i * 64 + c;
+    }
+    // the staging vector dies at the end of this block, so the copy is complete before it does:
+    // ordered on the stream after whatever still reads the table, then waited for
+    if (hipMemcpyAsync(table, host.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return hpe_fail(HPE_ERUNTIME, "%s: table copy: %s", who, hipGetErrorString(hipGetLastError()));
   }
-  hipStream_t s = (hipStream_t)stream;
-  // the staging vector dies on return, so the copy is complete before it does: ordered on the
-  // stream after whatever still reads the table, then waited for
-  if (hipMemcpyAsync(table, host.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: table copy: %s", hipGetErrorString(hipGetLastError()));
-  for (int i = 0; i < n_trials; ++i)  // flags and granules, as hpe_fit_epoch
+  // flags and granules: no tag of an earlier launch (an exact re-run, or iterations restored from
+  // a checkpoint) can match this launch's
+  for (int i = 0; i < n; ++i)
     if (hipMemsetAsync(trials[i].workspace, 0, hpe_fit_workspace_size(trials[i].prog, trials[i].batch), s) != hipSuccess)
-      return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: memset: %s", hipGetErrorString(hipGetLastError()));
-  if (hipFuncSetAttribute((const void*)fns.multi, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
-  hipLaunchKernelGGL(fns.multi, dim3(grid), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, FitArgs{}, (const FitEnt*)table,
-                     (const int*)((const unsigned char*)table + map_off));
-  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_fit_epoch_multi: launch failed");
+      return hpe_fail(HPE_ERUNTIME, "%s: memset: %s", who, hipGetErrorString(hipGetLastError()));
+  const fit_fn k = n == 1 ? fns.solo : fns.multi;
+  if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_BYTES) != hipSuccess)
+    return hpe_fail(HPE_ERUNTIME, "%s: LDS attribute: %s", who, hipGetErrorString(hipGetLastError()));
+  hipLaunchKernelGGL(k, dim3(grid), dim3(FIT_NW * 64), FIT_LDS_BYTES, s, solo, n == 1 ? nullptr : (const FitEnt*)table,
+                     n == 1 ? nullptr : (const int*)((const unsigned char*)table + map_off));
+  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s: launch failed", who);
   return HPE_OK;
 }
 
@@ -1127,5 +1119,5 @@ extern "C" int hpe_res_fit_epoch_multi(const hpe_fit_trial* trials, int32_t n_tr
       return hpe_fail(HPE_EINVAL, "hpe_res_fit_epoch_multi: trial %d: kernel instance %d differs from trial 0's %d "
                                   "(hpe_res_fit_multi_instance: one launch, one instance)", i, id, inst);
   }
-  return res_fit_multi_launch(trials, n_trials, table, (hipStream_t)stream);
+  return res_fit_multi_launch(trials, n_trials, table, (hipStream_t)stream, "hpe_res_fit_epoch_multi");
 }

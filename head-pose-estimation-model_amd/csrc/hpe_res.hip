@@ -767,30 +767,12 @@ int res_launch(const int* w, const Args& a, int grid, hipStream_t s) {
 // the epoch kernel's arguments of one (checked, KIND_RES) trial
 static ResFitArgs res_fit_args(const hpe_fit_trial& t) {
   ResFitArgs a = {};
-  a.prog = hpe_prog_dwords(t.prog);
-  a.params = t.params; a.params_t = t.params_t; a.m = t.m; a.v = t.v; a.l2 = t.l2; a.tpos = t.tpos;
-  a.x = t.x; a.ytrue = t.y_true; a.perm = t.perm;
-  a.n = (int)t.n; a.bs = t.batch; a.steps = (int)((t.n + t.batch - 1) / t.batch); a.kind = t.kind;
-  a.b1 = t.beta_1; a.b2 = t.beta_2; a.eps = t.epsilon;
-  a.alpha = t.alpha; a.seed_base = t.seed_base; a.iter0 = t.iter0;
-  a.stats = t.stats; a.stats_stride = t.stats_stride;
+  fit_trial_fields(t, &a);
   a.flags = (int*)t.workspace;
   return a;
 }
 
-int res_fit_launch(const hpe_fit_trial& t, hipStream_t s) {
-  const res_fit_fn f = res_pick(hpe_prog_words(t.prog)).fit;
-  if (!f) return 2;
-  const ResFitArgs a = res_fit_args(t);
-  const int lds = RES_LDS_BYTES;
-  hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  const int tv = hpe_tev_begin(s);
-  hipLaunchKernelGGL(f, dim3(1), dim3(RES_NW * 64), lds, s, a, (const ResFitEnt*)nullptr);
-  hpe_tev_end(s, tv);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-// ---- several residual-stack trials in one launch: block b trains trial b -------------------------
+// ---- the epoch launch: block b trains trial b -----------------------------------------------------
 int res_fit_instance(const int* w) {
   int id = -1;
   if (w[H_KIND] != KIND_RES || !res_supported(w) || !res_pick(w, &id).fit_multi) return -1;
@@ -799,27 +781,34 @@ int res_fit_instance(const int* w) {
 
 size_t res_fit_table_bytes(int n_trials) { return n_trials < 1 ? 0 : (size_t)n_trials * sizeof(ResFitArgs); }
 
-// trials: checked, KIND_RES, one shared instance (hpe_res_fit_epoch_multi); HPE_OK or hpe_fail's code
-int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s) {
-  const res_fit_fn f = res_pick(hpe_prog_words(trials[0].prog)).fit_multi;
-  if (!f) return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: no kernel");
-  std::vector<ResFitArgs> host(n_trials);
-  for (int i = 0; i < n_trials; ++i) host[i] = res_fit_args(trials[i]);
-  // the staging vector dies on return, so the copy is complete before it does: ordered on the
-  // stream after whatever still reads the table, then waited for
-  if (hipMemcpyAsync(table, host.data(), res_fit_table_bytes(n_trials), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: table copy: %s", hipGetErrorString(hipGetLastError()));
-  for (int i = 0; i < n_trials; ++i)  // the flags word, as hpe_fit_epoch
+// trials: checked, KIND_RES, one shared instance; HPE_OK or hpe_fail's code.  One trial runs the solo
+// entry on a grid of one, its arguments passed by value (no table, no wait); several run the multi
+// entry over the table
+int res_fit_multi_launch(const hpe_fit_trial* trials, int n_trials, void* table, hipStream_t s, const char* who) {
+  const ResFns fns = res_pick(hpe_prog_words(trials[0].prog));
+  const bool one = n_trials == 1;
+  const res_fit_fn f = one ? fns.fit : fns.fit_multi;
+  if (!f) return hpe_fail(HPE_ERUNTIME, "%s: no kernel", who);
+  if (!one) {
+    std::vector<ResFitArgs> host(n_trials);
+    for (int i = 0; i < n_trials; ++i) host[i] = res_fit_args(trials[i]);
+    // the staging vector dies with this block, so the copy is complete before it does: ordered on
+    // the stream after whatever still reads the table, then waited for
+    if (hipMemcpyAsync(table, host.data(), res_fit_table_bytes(n_trials), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return hpe_fail(HPE_ERUNTIME, "%s: table copy: %s", who, hipGetErrorString(hipGetLastError()));
+  }
+  for (int i = 0; i < n_trials; ++i)  // the flags word (hpe_fit_workspace_size)
     if (hipMemsetAsync(trials[i].workspace, 0, 64, s) != hipSuccess)
-      return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: memset: %s", hipGetErrorString(hipGetLastError()));
+      return hpe_fail(HPE_ERUNTIME, "%s: memset: %s", who, hipGetErrorString(hipGetLastError()));
   const int lds = RES_LDS_BYTES;
   if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-    return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: LDS attribute: %s", hipGetErrorString(hipGetLastError()));
+    return hpe_fail(HPE_ERUNTIME, "%s: LDS attribute: %s", who, hipGetErrorString(hipGetLastError()));
   const int tv = hpe_tev_begin(s);
-  hipLaunchKernelGGL(f, dim3(n_trials), dim3(RES_NW * 64), lds, s, ResFitArgs{}, (const ResFitEnt*)table);
+  hipLaunchKernelGGL(f, dim3(n_trials), dim3(RES_NW * 64), lds, s, one ? res_fit_args(trials[0]) : ResFitArgs{},
+                     one ? nullptr : (const ResFitEnt*)table);
   hpe_tev_end(s, tv);
-  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "hpe_res_fit_epoch_multi: launch failed");
+  if (hipGetLastError() != hipSuccess) return hpe_fail(HPE_ERUNTIME, "%s: launch failed", who);
   return HPE_OK;
 }
 #endif

@@ -6,7 +6,6 @@ arithmetic op of the hot path runs in libhpe.so (csrc/hpe_rowprog.hip) through t
 """
 import ctypes
 import os
-import warnings
 
 import numpy as np
 import torch
@@ -227,11 +226,16 @@ class Engine:
         _lib.check(lib.hpe_reduce(c.h, rows, _ptr(ws), _ptr(self.grad), _stream()), 'hpe_reduce')
         return self.grad
 
-    def optimizer_step(self, opt, stats, grad_scale=1.0):
+    def _opt_kind(self, opt):
+        """The optimizer's kind code; a non-SGD optimizer gets its m / v on first use."""
         kind = OPT_KIND[opt.kind]
         if kind and self.m is None:
             self.m = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
             self.v = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
+        return kind
+
+    def optimizer_step(self, opt, stats, grad_scale=1.0):
+        kind = self._opt_kind(opt)
         self.iterations += 1
         lib = _lib.load()
         pend = getattr(self, '_pending', None)
@@ -269,10 +273,7 @@ class Engine:
         RCCL on GPU ranks), the launches of the Python DP loop in the same order."""
         if P > 1 and self.spatial() is not None:
             raise ValueError('fit of attention heads runs on 1x1 maps (train_88.py:270-305)')
-        kind = OPT_KIND[opt.kind]
-        if kind and self.m is None:
-            self.m = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
-            self.v = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
+        kind = self._opt_kind(opt)
         c = self.program('train', P)
         lib = _lib.load()
         n = int(perm.numel())
@@ -367,14 +368,11 @@ class Engine:
             a = np.full(steps, lr)
         return a.astype(np.float32)
 
-    def _alphas(self, opt, steps):
-        return torch.from_numpy(self._alphas_host(opt, steps)).to(self.device)
-
     def _restore(self, saved):
-        for dst, src in zip([t for t in (self.params, self.params_t, self.m, self.v) if t is not None], saved):
+        for dst, src in zip(self.fit_state(), saved):
             dst.copy_(src)
 
-    # -- one trial of a multi-trial epoch launch (hpe/trials.py, hpe_fit_epoch_multi) -------------
+    # -- this engine as one trial of an epoch launch (the driver: hpe/trials.py) -------------------
     def fit_state(self):
         """The tensors an epoch launch updates in place (what a flagged epoch restores)."""
         return [t for t in (self.params, self.params_t, self.m, self.v) if t is not None]
@@ -384,13 +382,11 @@ class Engine:
         return self._fit_ws[1:2].view(torch.int32)
 
     def fit_trial(self, opt, x, y, perm, batch, stats, seed_base, alpha):
-        """hpe_fit_trial of this engine's next epoch: fit_epoch's arguments, with alpha (device
-        [steps], the values of _alphas_host) supplied by the caller."""
+        """hpe_fit_trial of this engine's next epoch: ceil(n / batch) steps over rows perm (device
+        int32) of x / y; stats: device [steps, >= 2 + 4 G]; alpha: device [steps], the values of
+        _alphas_host.  Sizes the epoch-launch workspace (flags word: fit_flag_word)."""
         c = self.program('train', 1)
-        kind = OPT_KIND[opt.kind]
-        if kind and self.m is None:
-            self.m = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
-            self.v = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
+        kind = self._opt_kind(opt)
         need = _lib.load().hpe_fit_workspace_size(c.h, int(batch))
         if getattr(self, '_fit_ws', None) is None or self._fit_ws.numel() * 4 < need:
             self._fit_ws = torch.zeros(max(need // 4, 16), dtype=torch.float32, device=self.device)
@@ -400,45 +396,3 @@ class Engine:
                              float(opt.learning_rate), float(opt.beta_1), float(opt.beta_2), float(opt.epsilon),
                              dp(alpha), int(seed_base) & 0xFFFFFFFFFFFFFFFF, int(self.iterations), dp(stats),
                              int(stats.shape[1]), dp(self._fit_ws))
-
-    def fit_epoch(self, opt, x, y, perm, batch, stats, seed_base):
-        """One epoch of fit: ceil(n / batch) steps over rows perm (device int32) of x / y in one
-        launch; stats: device [steps, >= 2 + G].  A flagged fp16-split overflow re-runs the epoch
-        on the exact-fp32 path from the saved state.  A workgroup-exchange timeout (flag 2: the G
-        workgroups were not all resident, e.g. another job held CUs) leaves workgroups at different
-        steps, so the saved parameters / Adam state are restored, the fused path is disabled for this
-        engine, and None is returned: the caller re-runs the epoch on the per-step path."""
-        c = self.program('train', 1)
-        lib = _lib.load()
-        kind = OPT_KIND[opt.kind]
-        if kind and self.m is None:
-            self.m = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
-            self.v = torch.zeros(self.n_train, dtype=torch.float32, device=self.device)
-        n = int(perm.numel())
-        steps = -(-n // int(batch))
-        alpha = self._alphas(opt, steps)
-        need = lib.hpe_fit_workspace_size(c.h, int(batch))
-        if getattr(self, '_fit_ws', None) is None or self._fit_ws.numel() * 4 < need:
-            self._fit_ws = torch.zeros(max(need // 4, 16), dtype=torch.float32, device=self.device)
-        saved = [t.clone() for t in (self.params, self.params_t, self.m, self.v) if t is not None]
-
-        def launch(exact):
-            _lib.check(lib.hpe_fit_epoch(
-                c.h, _ptr(self.params), _ptr(self.params_t), _ptr(self.m), _ptr(self.v), _ptr(self.l2),
-                _ptr(self.tpos), _ptr(x), _ptr(y), _ptr(perm), n, int(batch), kind, float(opt.learning_rate),
-                float(opt.beta_1), float(opt.beta_2), float(opt.epsilon), _ptr(alpha),
-                int(seed_base) & 0xFFFFFFFFFFFFFFFF, int(self.iterations), _ptr(stats), int(stats.shape[1]),
-                int(exact), _ptr(self._fit_ws), _stream()), 'hpe_fit_epoch')
-            return int(self._fit_ws[:2].view(torch.int32)[1].item())
-
-        flags = launch(0)
-        if flags & 1:  # fp16 range exceeded somewhere: redo the epoch exactly
-            self._restore(saved)
-            flags = launch(1)
-        if flags & 2:
-            self._restore(saved)
-            self._fit_disabled = True
-            warnings.warn('hpe_fit_epoch: workgroup exchange timed out; epoch re-run on the per-step path')
-            return None
-        self.iterations += steps
-        return steps

@@ -263,6 +263,17 @@ class Model:
         if self._dist is not None:
             dist, grp = self._dist
             world, rank = dist.get_world_size(grp), dist.get_rank(grp)
+        # the reference's regime (P = 1, create_model family or residual stack, one rank): the whole
+        # epoch is one launch, run by the driver hpe.fit_many shares (hpe/trials.py), this model its
+        # one trial; otherwise one train_step + reduce + optimizer per step, below
+        self._last_fit_fused = eng.fit_epoch_supported(bs, P, world)
+        if self._last_fit_fused:
+            from . import trials
+            t = trials._Trial(0, self, bs, hrandom.seed(), callbacks, n, '',
+                              'hpe_fit_epoch: workgroup exchange timed out')
+            valid = (vxd, vyd, vn) if validation_data is not None else None
+            return trials.run_epochs([t], trials.begin([t], epochs, verbose), xd, yd, valid, n, epochs,
+                                     initial_epoch, shuffle, verbose, None)[0]
         hist = History()
         cbs = [hist] + list(callbacks or [])
         for cb in cbs:
@@ -275,39 +286,27 @@ class Model:
         steps = math.ceil(n / bs)
         og = eng.optim_grid()
         stats = torch.zeros((steps, 2 + og), dtype=torch.float32, device=eng.device)
-        # the reference's regime (P = 1, create_model family, one rank): the whole epoch is one
-        # launch (csrc/hpe_fit.hip); otherwise one train_step + reduce + optimizer per step
-        fused = eng.fit_epoch_supported(bs, P, world)
-        self._last_fit_fused = fused
         # one bound on the resident rows per call: below the fp16 split's data range (64) the
         # per-step launches skip their exact-fp32 twin (csrc/hpe_mlp2.hip launch_pair)
-        x_bound = 0.0 if fused or not xd.numel() else max(-float(xd.amin().item()), float(xd.amax().item()))
+        x_bound = 0.0 if not xd.numel() else max(-float(xd.amin().item()), float(xd.amax().item()))
         if not np.isfinite(x_bound):
             x_bound = 0.0
-        if fused:  # [sse, sae, per-wave regularisation shares of the 4 G waves]
-            stats = torch.zeros((steps, 2 + 4 * eng.fit_groups()), dtype=torch.float32, device=eng.device)
         for epoch in range(initial_epoch, epochs):
             for cb in cbs:
                 cb.on_epoch_begin(epoch)
             perm = rng.permutation(n) if shuffle else np.arange(n)
             idx = torch.from_numpy(perm.astype(np.int32)).to(eng.device)
             nbs = [min(n, (s + 1) * bs) - s * bs for s in range(steps)]
-            if fused:
-                stats.zero_()
-                if eng.fit_epoch(self.optimizer, xd, yd, idx, bs, stats, hrandom.dropout_seed(0)) is None:
-                    # the epoch launch timed out and was rolled back: this and later epochs per step
-                    fused = self._last_fit_fused = False
-                    stats = torch.zeros((steps, 2 + og), dtype=torch.float32, device=eng.device)
-            # per-step path: the whole step loop in one C call (hpe_fit_steps; under data parallelism
+            # the whole step loop in one C call (hpe_fit_steps; under data parallelism
             # hpe_fit_steps_dp with a per-step all-reduce hook: the same launches as the loop below,
             # without a Python round trip per step); HPE_FIT_STEPS=0 keeps the Python loop
-            c_steps = not fused and os.environ.get('HPE_FIT_STEPS', '1') != '0'
+            c_steps = os.environ.get('HPE_FIT_STEPS', '1') != '0'
             if c_steps:
                 # (HPE_FIT_DP_ONE_RANK=1: the data-parallel step loop on a one-rank group, for tests)
                 dp = world > 1 or os.environ.get('HPE_FIT_DP_ONE_RANK') == '1'
                 eng.fit_steps(self.optimizer, xd, yd, idx, bs, stats, hrandom.dropout_seed(0), x_bound, P,
                               dist=self._dist if dp else None)
-            for s in range(0 if fused or c_steps else steps):
+            for s in range(0 if c_steps else steps):
                 b0, b1 = s * bs, min(n, (s + 1) * bs)
                 nb = b1 - b0
                 r0, r1 = batch_slice(b0, b1, rank, world)   # this rank's share of the batch

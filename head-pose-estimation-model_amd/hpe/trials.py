@@ -1,4 +1,11 @@
-"""fit_many: train independent models ("trials") side by side, several per epoch launch.
+"""The whole-epoch launch's one host driver (run_epochs), and fit_many: train independent models
+("trials") side by side, several per epoch launch.
+
+Model.fit's fused path is the driver with one trial, fit_many the driver with several: the epoch
+launch, the flag decoding, the exact re-run, the timeout rollback, the read-back and the callback
+loop exist once, so "model i ends bit-identical to its solo fit" is one code path, not two kept in
+step.  A launch of one trial runs the kernels' solo entry (hpe_fit_epoch_multi and
+hpe_res_fit_epoch_multi with n_trials = 1), of several the multi entry.
 
 The whole-epoch kernel of the reference's regime (csrc/hpe_fit.hip: 1x1 maps, the create_model
 family, batch <= 512) uses one workgroup per 32 hidden units in one eighth of its grid.
@@ -32,8 +39,12 @@ _MASK = 0xFFFFFFFFFFFFFFFF
 
 
 class _Trial:
-    def __init__(self, i, model, bs, seed, callbacks, n):
+    """One model of an epoch launch.  label prefixes its verbose line, timeout opens its warning
+    when the workgroup exchange times out: the caller's texts (Model.fit's or fit_many's)."""
+
+    def __init__(self, i, model, bs, seed, callbacks, n, label, timeout):
         self.i, self.model, self.bs, self.seed = i, model, bs, int(seed)
+        self.label, self.timeout = label, timeout
         self.eng = model._eng()
         self.res = self.eng.program('train', 1).prog.kind == 'res'   # one workgroup per trial, never flags
         self.steps = math.ceil(n / bs)
@@ -129,8 +140,11 @@ def _launch(trials, exact, tables, record):
             _lib.check(lib.hpe_res_fit_epoch_multi(arr, len(ts), tab, _lib.stream()), 'hpe_res_fit_epoch_multi')
             record.append([t.i for t in ts])
             continue
-        cap = lib.hpe_fit_multi_lane_cap(ts[0].eng.program('train', 1).h)
-        for idxs in plan_launches([t.eng.fit_groups() for t in ts], cap):
+        split = [[0]]   # one trial runs the kernel's solo entry (hpe_fit_supported): nothing to place
+        if len(ts) > 1:
+            cap = lib.hpe_fit_multi_lane_cap(ts[0].eng.program('train', 1).h)
+            split = plan_launches([t.eng.fit_groups() for t in ts], cap)
+        for idxs in split:
             arr = (_lib.FitTrial * len(idxs))(*[ts[j].ft for j in idxs])
             tab = table(lib.hpe_fit_multi_table_size(len(idxs)), dev)
             _lib.check(lib.hpe_fit_epoch_multi(arr, len(idxs), int(exact), tab, _lib.stream()), 'hpe_fit_epoch_multi')
@@ -171,14 +185,29 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
             raise ValueError('fit_many: validation_data must have x\'s channels on 1x1 maps')
     dev = models[0]._eng().device
     xd, yd = torch.from_numpy(rows).to(dev), torch.from_numpy(lab).to(dev)
+    val = None
     if validation_data is not None:
-        vxd, vyd = torch.from_numpy(vrows).to(dev), torch.from_numpy(vlab).to(dev)
-    trials = [_Trial(i, m, bss[i], seeds[i], callbacks[i], n) for i, m in enumerate(models)]
-    # every fused trial's stats in one buffer: one zero fill and one slice of the read-back per epoch
+        val = (torch.from_numpy(vrows).to(dev), torch.from_numpy(vlab).to(dev), vn)
+    trials = [_Trial(i, m, bss[i], seeds[i], callbacks[i], n, 'Model %d - ' % i,
+                     'hpe_fit_epoch_multi: workgroup exchange of model %d timed out' % i)
+              for i, m in enumerate(models)]
+    pool = begin(trials, epochs, verbose)
+    fit_many.last_plan = {'launches': [], 'flags': [], 'exact': []}
+    return run_epochs(trials, pool, xd, yd, val, n, epochs, initial_epoch, shuffle, verbose, fit_many.last_plan)
+
+
+fit_many.last_plan = None
+
+
+def begin(trials, epochs, verbose):
+    """Start training `trials`: every trial's fused stats rows [steps, 2 + 4 G] as slices of one pool
+    (one zero fill and one slice of the read-back per epoch), which is returned, and the callbacks'
+    train-begin calls."""
+    import torch
     offs = np.cumsum([0] + [t.steps * (2 + 4 * t.eng.fit_groups()) for t in trials])
-    pool = torch.zeros(int(offs[-1]), dtype=torch.float32, device=dev)
-    for t in trials:
-        t.stats = pool[int(offs[t.i]):int(offs[t.i + 1])].view(t.steps, -1)
+    pool = torch.zeros(int(offs[-1]), dtype=torch.float32, device=trials[0].eng.device)
+    for k, t in enumerate(trials):
+        t.stats = pool[int(offs[k]):int(offs[k + 1])].view(t.steps, -1)
         t.model._last_fit_fused = True
         for cb in t.cbs:
             cb.set_model(t.model)
@@ -186,17 +215,32 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
         t.model.stop_training = False
         for cb in t.cbs:
             cb.on_train_begin()
-    plan = fit_many.last_plan = {'launches': [], 'flags': [], 'exact': []}
+    return pool
+
+
+def run_epochs(trials, pool, xd, yd, valid, n, epochs, initial_epoch, shuffle, verbose, plan):
+    """The one driver of the whole-epoch launch, for Model.fit (one trial) and fit_many alike: per
+    epoch, one upload of every active trial's permutation and step sizes, the launches, one read-back
+    of flags, stats and validation sums, the exact re-run of trials whose fp16 range was exceeded, the
+    rollback of trials whose workgroup exchange timed out (fused path disabled for that engine, this
+    and later epochs through Engine.fit_steps), then logs and callbacks.  trials and pool: from
+    begin(); xd / yd: the n device rows and labels; valid: None, or (rows, labels, image count) of the
+    validation set; plan: None, or the dict that records each epoch's launches, flags words and
+    exact re-runs.  Returns the Histories."""
+    import torch
+    dev = xd.device
+    vxd, vyd, vn = valid or (None, None, 0)
+    vP = vxd.shape[0] // vn if vn else 1
     tables = []
 
-    def per_step(t, idx):   # Model.fit's per-step epoch of a trial whose fused path is disabled
+    def per_step(t, idx):   # the per-step epoch of a trial whose fused path is disabled
         t.eng.fit_steps(t.model.optimizer, xd, yd, idx, t.bs, t.stats, t.seed_base, 0.0, 1)
 
     def validate(t):
-        if validation_data is None:
+        if valid is None:
             return []
         e = t.eng
-        return [e.loss_sums(vxd, vyd, 1), (e.l2 * e.params[:e.n_train] ** 2).sum().reshape(1)]
+        return [e.loss_sums(vxd, vyd, vP), (e.l2 * e.params[:e.n_train] ** 2).sum().reshape(1)]
 
     for epoch in range(initial_epoch, epochs):
         act = [t for t in trials if t.active]
@@ -242,7 +286,7 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
                     o += c
                 flag = int(f.pop(0)[0]) if t.fused else 0
                 st = f[0].view(np.float32).reshape(t.steps, -1)
-                val = (f[1].view(np.float32), vn * 3, float(f[2].view(np.float32)[0])) if len(f) > 1 else None
+                val = (f[1].view(np.float32), vn * vP * 3, float(f[2].view(np.float32)[0])) if len(f) > 1 else None
                 out[t.i] = (flag, st, val)
             return out
 
@@ -262,19 +306,19 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
             for t in exact:
                 flags[t.i] |= again[t.i][0]
         timed = [t for t in redo if res[t.i][0] & 2]
-        if timed:   # as Model.fit: roll back, disable the fused path, this and later epochs per step
+        if timed:   # roll back, disable the fused path, this and later epochs per step
             for t in timed:
                 t.eng._restore(t.saved)
                 t.eng._fit_disabled = True
                 t.fused = t.model._last_fit_fused = False
-                warnings.warn('hpe_fit_epoch_multi: workgroup exchange of model %d timed out; epoch re-run on '
-                              'the per-step path' % t.i)
+                warnings.warn(t.timeout + '; epoch re-run on the per-step path')
                 t.stats = torch.zeros((t.steps, 2 + t.eng.optim_grid()), dtype=torch.float32, device=dev)
                 per_step(t, t.idx)
             res.update(read_back(timed))
-        plan['launches'].append(record)
-        plan['flags'].append([flags.get(i, 0) for i in range(T)])
-        plan['exact'].append([t.i for t in exact])
+        if plan is not None:
+            plan['launches'].append(record)
+            plan['flags'].append([flags.get(t.i, 0) for t in trials])
+            plan['exact'].append([t.i for t in exact])
         for t in act:
             if t.fused:
                 t.eng.iterations += t.steps
@@ -283,7 +327,7 @@ def fit_many(models, x, y, batch_size, epochs=1, seeds=None, validation_data=Non
             logs = epoch_logs(st, t.nbs, n, 1, val)
             t.model.optimizer.iterations = t.eng.iterations
             if verbose and verbose != 0:
-                print('Model %d - Epoch %d/%d - ' % (t.i, epoch + 1, epochs) +
+                print(t.label + 'Epoch %d/%d - ' % (epoch + 1, epochs) +
                       ' - '.join('%s: %.4f' % (k, v) for k, v in logs.items()))
             for cb in t.cbs:
                 cb.on_epoch_end(epoch, logs)
@@ -302,6 +346,3 @@ def _end(t):
         cb.on_train_end()
     t.model.history = t.hist
     t.hist.model = t.model
-
-
-fit_many.last_plan = None

@@ -213,7 +213,10 @@ int hpe_fit_epoch(const hpe_program *prog, float *params, float *params_t, float
  * hpe_fit_epoch_multi: one launch for all trials (HPE_EINVAL if !hpe_fit_multi_supported); zeroes
  * every trial's workspace first.  table: hpe_fit_multi_table_size(n_trials) bytes of device memory,
  * written here through the stream (the call waits for that copy; the table must stay untouched
- * until the launch has finished). */
+ * until the launch has finished).  With n_trials == 1 the call is hpe_fit_epoch of that trial: the
+ * same launch (the trial's arguments by value on its 8 G grid), so the table, still required, is
+ * neither written nor waited for.  hpe_fit_epoch is that one-trial case with its arguments spread
+ * out. */
 typedef struct hpe_fit_trial {
   const hpe_program *prog;
   float *params, *params_t, *m, *v;
@@ -265,7 +268,9 @@ int hpe_fit_epoch_multi(const hpe_fit_trial *trials, int32_t n_trials, int32_t e
  * checks, kind res, stats_stride >= 3, one shared instance; otherwise HPE_EINVAL with a message that
  * names the trial), zeroes each trial's workspace, writes the table through the stream (the call
  * waits for that copy; the table must stay untouched until the launch has finished) and makes one
- * launch of n_trials workgroups. */
+ * launch of n_trials workgroups.  With n_trials == 1 the call is hpe_fit_epoch of that trial: the
+ * same launch on a grid of one with the arguments passed by value; the table, still required, is
+ * neither written nor waited for. */
 int hpe_res_fit_multi_instance(const hpe_program *prog);
 int hpe_res_fit_multi_instance_words(const int32_t *words, int64_t n_words);
 size_t hpe_res_fit_multi_table_size(int32_t n_trials);

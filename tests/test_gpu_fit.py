@@ -173,3 +173,18 @@ def test_fused_epoch_timeout_rolls_back_to_per_step():
         np.testing.assert_array_equal(wf[k], wp[k], err_msg=k)
     np.testing.assert_allclose(hf.history['loss'], hp.history['loss'], rtol=1e-6)
     assert mf._eng().iterations == mp._eng().iterations == 2 * 4
+
+
+def test_fused_fit_leaves_fit_many_last_plan_alone():
+    """Model.fit's fused path is the epoch driver hpe.fit_many uses, with one trial; the launch
+    record fit_many.last_plan belongs to fit_many calls alone."""
+    x, y = features(300, 96, seed=41), labels(300, seed=42)
+    prev = hpe.fit_many.last_plan
+    try:
+        for mark in (None, {'launches': ['kept']}):
+            hpe.fit_many.last_plan = mark
+            h = _fit(_model('new', F=64), 'adam', 2.8e-4, x, y, 128, 2, fused=True)
+            assert len(h.history['loss']) == 2
+            assert hpe.fit_many.last_plan is mark and mark in (None, {'launches': ['kept']})
+    finally:
+        hpe.fit_many.last_plan = prev

@@ -426,3 +426,52 @@ def test_global_seed_state_is_untouched():
     for i, s in enumerate(specs):
         ref, href = _solo(dict(s, seed=1234 + i), x, y, 1)
         _same(ms[i], hs[i], ref, href, 'trial %d' % i)
+
+
+def test_one_trial_multi_call_equals_hpe_fit_epoch():
+    """The argument packing of the two wrappers: hpe_fit_epoch and hpe_fit_epoch_multi with
+    n_trials = 1 run the same solo entry, so two clones of one state (300 rows at batch 128: two
+    full batches and a ragged one of 44; Adam with non-zero m / v, dropout 0.2) end byte-equal in
+    params, mirror, m, v, the stats rows and the flags word."""
+    import torch
+    from hpe.engine import OPT_KIND
+    lib = _lib.load()
+    n, bs, steps = 300, 128, 3
+    m = _compiled(_spec(F=64, dropout=0.2))
+    eng, opt = m._eng(), m.optimizer
+    dev = eng.device
+    x, y = features(n, 96, seed=32), labels(n, seed=33)
+    xd, yd = torch.from_numpy(x.reshape(n, 96)).to(dev), torch.from_numpy(y).to(dev)
+    perm = torch.from_numpy(np.random.RandomState(3).permutation(n).astype(np.int32)).to(dev)
+    alpha = torch.from_numpy(eng._alphas_host(opt, steps)).to(dev)
+    h = eng.program('train', 1).h
+    assert lib.hpe_fit_supported(h, bs) == 1
+    st = {'params': eng.params.repeat(2, 1), 'params_t': eng.params_t.repeat(2, 1),
+          'm': (torch.rand(eng.n_train, device=dev) * 1e-3).repeat(2, 1),
+          'v': (torch.rand(eng.n_train, device=dev) * 1e-6).repeat(2, 1),
+          'stats': torch.zeros(2, steps, 2 + 4 * eng.fit_groups(), device=dev),
+          'ws': torch.full((2, lib.hpe_fit_workspace_size(h, bs) // 4), 7, dtype=torch.int32, device=dev)}
+
+    def trial(i):
+        dp = lambda t: t[i].data_ptr()  # noqa: E731
+        return _lib.FitTrial(h.value, dp(st['params']), dp(st['params_t']), dp(st['m']), dp(st['v']),
+                             eng.l2.data_ptr(), eng.tpos.data_ptr(), xd.data_ptr(), yd.data_ptr(), perm.data_ptr(),
+                             n, bs, OPT_KIND[opt.kind], float(opt.learning_rate), float(opt.beta_1),
+                             float(opt.beta_2), float(opt.epsilon), alpha.data_ptr(), 12345, 0,
+                             dp(st['stats']), int(st['stats'].shape[2]), dp(st['ws']))
+
+    t = trial(0)
+    _lib.check(lib.hpe_fit_epoch(t.prog, t.params, t.params_t, t.m, t.v, t.l2, t.tpos, t.x, t.y_true, t.perm, t.n,
+                                 t.batch, t.kind, t.lr, t.beta_1, t.beta_2, t.epsilon, t.alpha, t.seed_base, t.iter0,
+                                 t.stats, t.stats_stride, 0, t.workspace, _lib.stream()), 'hpe_fit_epoch')
+    table = torch.zeros(lib.hpe_fit_multi_table_size(1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.hpe_fit_epoch_multi((_lib.FitTrial * 1)(trial(1)), 1, 0, _lib.ptr(table), _lib.stream()),
+               'hpe_fit_epoch_multi')
+    torch.cuda.synchronize()
+    assert not torch.equal(st['params'][0], eng.params)      # the epoch trained something
+    assert (st['stats'][:, :, 0] > 0).all()
+    for k in ('params', 'params_t', 'm', 'v', 'stats'):
+        got = st[k].cpu().numpy().view(np.uint8).reshape(2, -1)
+        assert np.array_equal(got[0], got[1]), k
+    ws = st['ws'].cpu().numpy()
+    assert ws[0, 1] == ws[1, 1] != 7          # the flags word: zeroed from its 7, then equal

@@ -254,6 +254,34 @@ def test_more_trials_than_cus_at_the_c_abi():
     assert np.isfinite(st['stats'].cpu().numpy()).all() and (st['stats'][:, :, 0] > 0).all()
 
 
+def test_one_trial_multi_call_equals_hpe_fit_epoch():
+    """The argument packing of the two wrappers: hpe_fit_epoch and hpe_res_fit_epoch_multi with
+    n_trials = 1 run the same solo entry on a grid of one, so two clones of one state
+    (create_model_complex, 100 rows at batch 64: a ragged last batch of 36) end byte-equal in
+    params, mirror, m, v, the stats rows and the flags word."""
+    lib = _lib.load()
+    n, bs = 100, 64
+    m = _compiled(_spec(_complex_config(dr=0.1), opt='adam'))
+    assert _is_res(m)
+    x, y = features(n, 88, seed=15), labels(n, seed=16)
+    st, trials = _clone_trials(m, x, y, 1, n, bs)
+    table = torch.zeros(lib.hpe_res_fit_multi_table_size(1), dtype=torch.uint8, device=m._eng().device)
+    _lib.check(lib.hpe_res_fit_epoch_multi((_lib.FitTrial * 1)(trials[0]), 1, _lib.ptr(table), _lib.stream()),
+               'hpe_res_fit_epoch_multi')
+    t = trials[1]
+    _lib.check(lib.hpe_fit_epoch(t.prog, t.params, t.params_t, t.m, t.v, t.l2, t.tpos, t.x, t.y_true, t.perm, t.n,
+                                 t.batch, t.kind, t.lr, t.beta_1, t.beta_2, t.epsilon, t.alpha, t.seed_base, t.iter0,
+                                 t.stats, t.stats_stride, 0, t.workspace, _lib.stream()), 'hpe_fit_epoch')
+    torch.cuda.synchronize()
+    assert not torch.equal(st['params'][0], m._eng().params)      # the epoch trained something
+    assert (st['stats'][:, :, 0] > 0).all()
+    for k in ('params', 'params_t', 'm', 'v', 'stats'):
+        got = st[k].cpu().numpy().view(np.uint8).reshape(2, -1)
+        assert np.array_equal(got[0], got[1]), k
+    ws = st['ws'].cpu().numpy()
+    assert ws[0, 1] == ws[1, 1] == 0          # the flags word, zeroed from its 7 and never raised
+
+
 def test_early_stopping_at_different_epochs():
     """Patience 1, 2 and 4 with a min_delta no epoch can reach: trial i stops after epoch index
     patience_i, whatever the losses are, and is absent from the launches after that."""
