@@ -30,8 +30,10 @@
 // (P = 1 batches of 128 rows, latency-bound) 25 % slower; mlp2_launch picks by launch size.
 #ifdef MLP2_BIG
 #define MLP2_NS mlp2_big
+#define MLP2_BIG_OBJ 1
 #else
 #define MLP2_NS mlp2_small
+#define MLP2_BIG_OBJ 0
 #endif
 #define MLP2_BIG_ROWS (1 << 15)   // rows per launch from which the MLP2_BIG object runs
 namespace MLP2_NS {
@@ -100,6 +102,11 @@ __device__ __forceinline__ float e_bwd(const E2& e, uint64_t seed, int64_t img, 
 // labels of the tile's rows for the loss: 2 x 64 dwords by wave 0.  Gather mode (fit's shuffled
 // batches): lane l looks up the source image of tile row l once, before any piece is issued, so
 // the only wait in here never drains an in-flight prefetch.
+// NOW (the pre-split kernels of the big object): the label rows' source image by a ds_bpermute at the
+// row's own lane address (rows < 32: no wrap term) — __shfl's lane-id term is one value hoisted to
+// kernel entry, and at that kernel's register budget it sat in scratch, reloaded per tile.  Under the
+// small object's flags the bpermute costs a spill instead (+0.2 us on a 128-row step): __shfl there
+template <bool NOW = false>
 __device__ __forceinline__ void stage_tile(const Args& args, float* xs, float* lab, int64_t row0,
                                            const TileImg& ti, int wave, int NCB, int lane, int Cin,
                                            bool labels, int XS = MLP2_XS) {
@@ -135,7 +142,7 @@ __device__ __forceinline__ void stage_tile(const Args& args, float* xs, float* l
     for (int pc = 0; pc < 2; ++pc) {
       const int slot = pc * 64 + lane;
       const int r = min(slot >> 2, last), j = min(slot & 3, 2);
-      const int64_t src = __shfl(lsrc, r, 64);
+      const int64_t src = NOW ? __builtin_amdgcn_ds_bpermute(r << 2, lsrc) : __shfl(lsrc, r, 64);
       glds4(args.ytrue + src * 3 + j, lds_addr(lab + pc * 64));
     }
   }
@@ -193,28 +200,41 @@ typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 // One split of the landed X tile per workgroup instead of one per wave (the 12 waves all read the
 // whole tile, by rows and by columns): every thread turns 8 floats into the three data-side fp16
 // fragments (ch, cl, h of split_d8), written into ONE image
-//   xf[r][48 h + m] = X[r][KH h + m] (zero for m >= KH), fragment f at xf + f * 32 * FS,
+//   xf[img_row(r)][48 h + m] = X[r][KH h + m] (zero for m >= KH), fragment f at xf + f * 32 * FS,
 // that both GEMMs read:
-//   * forward: lane (row r, half h) reads K-step s as one b128 per fragment at 48 h + 8 s;
+//   * forward: lane (row r, half h) reads K-step s as one b128 per fragment at 48 h + 8 s of image
+//     row img_row(r);
 //   * dW1 (A = X^T): ds_read_b64_tr_b16 (tr_read8), which hands each lane one channel's values of
 //     four rows — no second, transposed image and no second split of the tile.
+// The rows are stored swapped (img_row: bits 0-1 <-> bits 2-3 of the tile row), so the four rows
+// R0 .. R0 + 3 that one transposed read addresses lie 4 image rows = 208 dwords = 16 banks apart:
+// each 32-lane group's four 16-dword spans tile the 64 banks, 2 LDS cycles per read where adjacent
+// rows (52 dwords apart, neighbours overlapping in 4 banks) took 4.  The forward's b128 reads stay at
+// 4 cycles and the pre-split's stores take 8 (10-11 unswapped); tests/test_lds_image_swap.py.
 // img_pos is the position of channel c in a row: at KH = 44 the second half starts at position 48
 // (16-byte aligned), so channels >= 44 sit 4 further on; positions [KH, 48) of both halves hold zeros,
 // and the pad channels [C_in, 96) of the raw tile hold zeros.  A 4-channel chunk never straddles the
 // gap; the chunks wholly past the image (channels 92..95 at KH = 44) map to the zeros at 92..95.
+// (a position within a row: the row swap of img_row does not touch it)
 template <int KH>
 __device__ __forceinline__ int img_pos(int c) {
   if (KH == 48) return c;
   return c < KH ? c : min(c + 48 - KH, 92);
 }
-// dW1's A operand of one (K-step, 32-channel block, fragment): rows R0 .. R0 + 3 and R0 + 8 .. R0 + 11
-// of the block's 32 channels, delivered channel-on-lane (lane 16 g + i of a half: channel 16 g + i;
-// element j: row R0 + 8 (j >> 2) + (j & 3)).  p is the lane's address: lane 16 g + 4 q + p' supplies
-// (row R0 + q, channels 16 g + 4 p' .. + 3), 8-byte aligned.  EXEC must be all ones here.
+// tile row -> image row: bits 0-1 <-> bits 2-3, so tile row 16 s + 8 rd + 4 h + q is image row
+// 16 s + 4 q + 2 rd + h.  The one place the map is written: the pre-split stores through it, the
+// forward reads through it, and the transposed reader's lane term / second-read offset are its image
+// of (h, q) / rd
+__device__ __forceinline__ constexpr int img_row(int r) { return (r & 16) | ((r & 3) << 2) | ((r >> 2) & 3); }
+// dW1's A operand of one (K-step, 32-channel block, fragment): tile rows R0 .. R0 + 3 and R0 + 8 ..
+// R0 + 11 of the block's 32 channels, delivered channel-on-lane (lane 16 g + i of a half: channel
+// 16 g + i; element j: row R0 + 8 (j >> 2) + (j & 3)).  p is the lane's address: lane 16 g + 4 q + p'
+// supplies (image row img_row(R0 + q), channels 16 g + 4 p' .. + 3), 8-byte aligned; tile row + 8 is
+// image row + 2 (img_row), the second read.  EXEC must be all ones here.
 __device__ __forceinline__ h8 tr_read8(const _Float16* p) {
   typedef __attribute__((address_space(3))) fp16x4* lp;
   const fp16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp)(p));
-  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp)(p + 8 * MLP2_FS));
+  const fp16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lp)(p + img_row(8) * MLP2_FS));
   return __builtin_shufflevector(__builtin_bit_cast(h4, a), __builtin_bit_cast(h4, b), 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // A1 park of a wave: accumulator register g's 64 lanes at row a1_row(g), 68 floats per row slot, so
@@ -245,7 +265,7 @@ __device__ __forceinline__ bool presplit_tile(const float* xs, _Float16* xf, int
 #pragma unroll
     for (int j = 0; j < 8; ++j) out |= !(fabsf(v[j]) < MLP2_X_LIMIT);
     const SplitD d8 = split_d8(v);
-    _Float16* d = xf + r * MLP2_FS + 48 * h + m0;
+    _Float16* d = xf + img_row(r) * MLP2_FS + 48 * h + m0;
     *(h8*)(d) = d8.ch;
     *(h8*)(d + 32 * MLP2_FS) = d8.cl;
     *(h8*)(d + 64 * MLP2_FS) = d8.h;
@@ -338,6 +358,16 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   float* red = hacc + NCB * 64 * HS;  // [2 * MLP2_MAXW]: block reduction of the loss sums
   float* colt = red + MLP2_RED;   // [NCB * 32][4]: per hidden unit (inv1, b1, s2, -), re-read per tile
   _Float16* xfb = (_Float16*)(colt + NCB * 128);  // PRE: [2 parities][3][32][MLP2_FS] ch, cl, h
+  // PRE, big object: dz2, which the backward reads as broadcast b128 rows, is packed [T][3], no pad
+  // float: a lane half's four consecutive rows 8 k + 4 h .. + 3 are 48 contiguous, 16-byte aligned
+  // bytes, three ds_read_b128 where four stood.  Elements are picked by compile-time index in the
+  // unrolled loop; the FMAs and their order are those of the padded table.  The small object keeps the
+  // padded table: its launches (< MLP2_BIG_ROWS rows, a tile or two per workgroup) are latency-bound,
+  // and under its flags the packed reads spill 16 B more in the loop (+0.35 us on a 128-row step).
+  // (The W2 table packed the same way for the head partials, twelve reads for sixteen, measured
+  // inside the noise and is not kept: DESIGN.md)
+  constexpr bool DZ2P = PRE && MLP2_BIG_OBJ;
+  constexpr int DZS = DZ2P ? 3 : 4;
 
   E2 e1 = {o[O_EACT], o[O_EDROP], (uint32_t)o[O_ETHR], __int_as_float(o[O_EKEEP])};
   E2 e2 = {o[O_AUX2], o[O_TBASE], (uint32_t)o[O_TCOUNT], __int_as_float(o[O_F0])};
@@ -365,7 +395,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   const int64_t xstep = CONTIG ? (int64_t)gridDim.x * T * Cin : 0;
   if (blockIdx.x < ntiles) {
     if constexpr (CONTIG) stage_contig(args, xbuf, lbuf, xnext, (int64_t)blockIdx.x * T, ti, wave, NCB, Cin, labels);
-    else stage_tile(args, xbuf, lbuf, (int64_t)blockIdx.x * T, ti, wave, NCB, lane, Cin, labels);
+    else stage_tile<PRE && MLP2_BIG_OBJ>(args, xbuf, lbuf, (int64_t)blockIdx.x * T, ti, wave, NCB, lane, Cin, labels);
   }
   xnext += xstep;
   const int nc = min(n, F - 1);
@@ -540,7 +570,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
                      wave, NCB, Cin, labels);
         xnext += xstep;
       } else {
-        stage_tile(args, xbuf + (PRE ? 0 : (buf ^ 1)) * MLP2_XF, lbuf + (buf ^ 1) * MLP2_LAB,
+        stage_tile<PRE && MLP2_BIG_OBJ>(args, xbuf + (PRE ? 0 : (buf ^ 1)) * MLP2_XF, lbuf + (buf ^ 1) * MLP2_LAB,
                    (int64_t)(tile + gridDim.x) * T, tn, wave, NCB, tlane, Cin, labels);
       }
     }
@@ -552,7 +582,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       const float* ap = xs + tl32 * MLP2_XS + thalf * KH;
       f32x16 acc = {};
       if constexpr (PRE) {
-        const _Float16* fp = xfb + buf * MLP2_IMG + tl32 * MLP2_FS + 48 * thalf;
+        const _Float16* fp = xfb + buf * MLP2_IMG + img_row(tl32) * MLP2_FS + 48 * thalf;
         // two-deep fragment buffer: the three reads of K-step s + 1 are issued before K-step s's
         // MFMAs, so an MFMA waits for reads a whole K-step old, not for its own fragment's round trip
         auto frag = [&](int s) {
@@ -715,7 +745,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         }
         if (train) {
           g = ACT1 >= 0 ? (d2 ? (k2 ? g / e2.keep : 0.f) : g) : e_bwd(e2, args.seed, img, j, g, p);
-          dz2[r * 4 + j] = g;
+          dz2[r * DZS + j] = g;
           ha2 += g;
         }
         hacc[ttid * HS + 0] = ha0;
@@ -752,14 +782,13 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
       // scaled, unscaled once at the flush
       const f32x4 w2v = PRE ? f32x4{w2r.x * s2, w2r.y * s2, w2r.z * s2, 0.f} : w2r;
       // dZ1 of accumulator register g (row (g & 3) + 8 (g >> 2) + 4 h), dW2 / db1 on the way
-      auto dz_of = [&](int g) {
-        const int r = (g & 3) + 8 * (g >> 2) + 4 * thalf;
-        const f32x4 d = *(const f32x4*)(dz2 + r * 4);
+      // (dx, dy, dz): the row's dZ2
+      auto dz_row = [&](int g, float dx, float dy, float dz) {
         const float a = a1s[wave * A1S + (PAD1 ? a1_row(g) : 64 * g) + tlane];
         // PRE: the fused form this sum compiles to, spelled out — with the scale folded into w2v the
         // bits stay the same only in that form, in every instantiation
-        const float da = PRE ? fmaf(d.z, w2v.z, fmaf(d.x, w2v.x, d.y * w2v.y))
-                             : d.x * w2v.x + d.y * w2v.y + d.z * w2v.z;
+        const float da = PRE ? fmaf(dz, w2v.z, fmaf(dx, w2v.x, dy * w2v.y))
+                             : dx * w2v.x + dy * w2v.y + dz * w2v.z;
         float gz, av = a;
         if (DROP) {
           gz = (dmask >> g) & 1u ? da * inv_keep1 : 0.f;
@@ -777,27 +806,51 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
           gz = LEAN || tok ? gz * act1_g<ACT1>(e1.act, av) : 0.f;
           db1 += gz;
         }
-        dw2[0] = fmaf(a, d.x, dw2[0]);
-        dw2[1] = fmaf(a, d.y, dw2[1]);
-        dw2[2] = fmaf(a, d.z, dw2[2]);
+        dw2[0] = fmaf(a, dx, dw2[0]);
+        dw2[1] = fmaf(a, dy, dw2[1]);
+        dw2[2] = fmaf(a, dz, dw2[2]);
         return gz;
+      };
+      // the padded table: one broadcast b128 per row
+      auto dz_of = [&](int g) {
+        const int r = (g & 3) + 8 * (g >> 2) + 4 * thalf;
+        const f32x4 d = *(const f32x4*)(dz2 + r * 4);
+        return dz_row(g, d.x, d.y, d.z);
+      };
+      // DZ2P: K-step s's eight dZ1 (accumulator registers 8 s .. 8 s + 7) from the packed table: the four
+      // rows 8 k + 4 h .. + 3 of k = 2 s, 2 s + 1 are twelve floats each, three b128; row q's dZ2 at 3 q
+      auto dz_step = [&](int s) {
+        f32x8 dv;
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const float* dp = dz2 + (8 * (2 * s + k2) + 4 * thalf) * 3;
+          const f32x4 t0 = *(const f32x4*)(dp), t1 = *(const f32x4*)(dp + 4), t2 = *(const f32x4*)(dp + 8);
+          const float t[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dv[4 * k2 + q] = dz_row(8 * s + 4 * k2 + q, t[3 * q], t[3 * q + 1], t[3 * q + 2]);
+        }
+        return dv;
       };
       if constexpr (PRE) {
         // dZ1 of K-step 0 -> split -> its 9 MFMAs, with the VALU of K-step 1's dZ1 free to issue
         // under them (no scheduling fences between the two), then K-step 1's MFMAs
         // The A operand X^T by transposed reads of this tile's image (tr_read8): K-step s, lane half
         // h, element j <-> tile row 16 s + 8 (j >> 2) + 4 h + (j & 3), so R0 = 16 s + 4 h; lane
-        // 16 g + 4 q + p of the half addresses row R0 + q, channels 32 kb + 16 g + 4 p .. + 3.  One lane
-        // term recomputed per tile; K-step, block (at KH = 48) and fragment are immediate offsets
+        // 16 g + 4 q + p of the half addresses tile row R0 + q = image row 16 s + 4 q + h (img_row),
+        // channels 32 kb + 16 g + 4 p .. + 3.  One lane term recomputed per tile; K-step, block (at
+        // KH = 48) and fragment are immediate offsets
         const int tc = (tl32 & 16) + 4 * (tl32 & 3);
-        const _Float16* th = xfb + buf * MLP2_IMG + (4 * thalf + ((tl32 >> 2) & 3)) * MLP2_FS;
+        const _Float16* th = xfb + buf * MLP2_IMG + img_row(4 * thalf + ((tl32 >> 2) & 3)) * MLP2_FS;
         auto xt_of = [&](int s, int kb) {
           const _Float16* q = th + 16 * s * MLP2_FS + img_pos<KH>(32 * kb + tc);
           return SplitD{tr_read8(q), tr_read8(q + 32 * MLP2_FS), tr_read8(q + 64 * MLP2_FS)};
         };
         f32x8 dv0, dv1;
+        if constexpr (DZ2P) dv0 = dz_step(0);
+        else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dv0[j] = dz_of(j);
+          for (int j = 0; j < 8; ++j) dv0[j] = dz_of(j);
+        }
         const SplitW d0 = split_w8_mix(dv0);
         __builtin_amdgcn_sched_barrier(0);
         // (no fence between the blocks: all 18 reads of the K-step may be in flight at once.  Their 36
@@ -806,8 +859,11 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         // tighter budget needed before, measured 1.2 % slower on the Model-96 step, A/B x3)
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) dw[kb] = mfma3_dw(xt_of(0, kb), d0, dw[kb]);
+        if constexpr (DZ2P) dv1 = dz_step(1);
+        else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dv1[j] = dz_of(8 + j);
+          for (int j = 0; j < 8; ++j) dv1[j] = dz_of(8 + j);
+        }
         __builtin_amdgcn_sched_barrier(0);
         const SplitW d1 = split_w8_mix(dv1);
 #pragma unroll
