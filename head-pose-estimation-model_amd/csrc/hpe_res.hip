@@ -555,7 +555,16 @@ static_assert(sizeof(ResFitEnt) == sizeof(ResFitArgs), "a table entry is a ResFi
 template <typename A>
 __device__ __forceinline__ float res_opt_one(const A& a, float alpha, float wi, float c2, float g, float& mi,
                                              float& vi) {
-  const float gr = fmaf(g, 1.f, 2.f * c2 * wi);
+  // optim_update's fmaf(g, gscale, 2 c2 w) at gscale = 1 is g + round(2 c2 w).  Written as
+  // fmaf(g, 1.f, ...) here, the constant 1 folds to a plain add that then contracts with the product
+  // into fma(2 c2, w, g), whose unrounded product differs in the last bit wherever the gradient is
+  // not large beside the regularisation term: contraction stays off for these two operations
+  float gr;
+  {
+#pragma clang fp contract(off)
+    const float r = 2.f * c2 * wi;
+    gr = g + r;
+  }
   if (a.kind == HPE_OPT_SGD) return wi - alpha * gr;
   if (a.kind == HPE_OPT_ADAM) {
     mi += (gr - mi) * (1.f - a.b1);

@@ -34,10 +34,12 @@ def activation(name, x):
         return x / (1.0 + x.abs())
     if name == 'sigmoid':
         return torch.sigmoid(x)
+    # expm1 of the clamped argument: the branch `where` drops must not overflow (exp(89) in fp32),
+    # or autograd multiplies its inf by the zero mask and the gradient is NaN
     if name == 'elu':
-        return torch.where(x > 0, x, torch.expm1(x))
+        return torch.where(x > 0, x, torch.expm1(x.clamp(max=0)))
     if name == 'selu':
-        return SELU_SCALE * torch.where(x > 0, x, SELU_ALPHA * torch.expm1(x))
+        return SELU_SCALE * torch.where(x > 0, x, SELU_ALPHA * torch.expm1(x.clamp(max=0)))
     if name == 'swish':
         return x * torch.sigmoid(x)
     if name == 'softplus':

@@ -19,8 +19,6 @@ conv2d_3/kernel at P = 9, where the fp32 oracle's worst tensor is 2.2e-6); every
 The CPU half (test_compiler_synth.py) holds the compiler's lowering of the same graphs to the
 oracle through the numpy emulator, so a failure here alone is the kernel's.
 """
-import time
-
 import numpy as np
 import pytest
 import torch
@@ -30,7 +28,7 @@ import synth_graphs as SG
 from hpe import _lib
 from hpe.engine import Engine
 from oracle import keras_ref as K
-from util import features, input_channels, labels, oracle_step
+from util import check_gradient, features, input_channels, labels
 
 pytestmark = pytest.mark.gpu
 
@@ -67,38 +65,7 @@ def _launch(eng, x, y, P, idx=None, img_off=0):
 
 
 def _check(tag, mc, w, eng, g, x, y, img_off=0):
-    """The kernel's gradient g (n_train + 4 words) against the float64 oracle on (x, y) in batch
-    order: whole-gradient bar, per-tensor bar from the fp32 oracle, loss sums.  Returns the worst
-    (kernel, fp32-oracle) per-tensor errors."""
-    t0 = time.time()
-    g64, sse, sae = oracle_step(mc, w, x, y, eng.layout, SEED, image_offset=img_off)
-    g32 = oracle_step(mc, w, x, y, eng.layout, SEED, image_offset=img_off, dtype=torch.float32)[0]
-    npt = eng.n_train
-    assert g.shape[0] == npt + 4 and g64.shape[0] == npt
-    assert np.isfinite(g).all()
-    err = np.abs(g[:npt] - g64).max() / np.abs(g64).max()
-    worst = (0.0, 0.0, '')
-    fails = []
-    for k, (o, shp) in eng.layout.param_index.items():
-        sl = slice(o, o + int(np.prod(shp)))
-        scale = np.abs(g64[sl]).max()
-        if scale == 0.0:
-            if np.any(g[sl] != 0.0):
-                fails.append((k, 'float64 gradient is zero, kernel max |g| = %.2e' % np.abs(g[sl]).max()))
-            continue
-        ek = np.abs(g[sl] - g64[sl]).max() / scale
-        e32 = np.abs(g32[sl] - g64[sl]).max() / scale
-        if ek > worst[0]:
-            worst = (ek, e32, k)
-        if ek > max(1e-5, 4 * e32):
-            fails.append((k, 'kernel %.2e, fp32 oracle %.2e' % (ek, e32)))
-    print('%s: max |g - g64| / max |g64| = %.2e; worst tensor %s: kernel %.2e, fp32 oracle %.2e (oracle %.1f s)'
-          % (tag, err, worst[2], worst[0], worst[1], time.time() - t0))
-    assert err <= 1e-5, err
-    assert not fails, fails
-    np.testing.assert_allclose(g[npt], sse, rtol=1e-5)
-    np.testing.assert_allclose(g[npt + 1], sae, rtol=1e-5)
-    return worst
+    return check_gradient(tag, mc, w, eng, g, x, y, SEED, img_off=img_off)
 
 
 def _first_layer_spread(mc, w, x):

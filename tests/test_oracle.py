@@ -114,3 +114,18 @@ def test_legacy_adam_matches_closed_form():
         v += (g * g - v) * 0.001
         x -= 0.1 * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t) * m / (np.sqrt(v) + 1e-7)
         assert abs(w['w'].item() - x) < 1e-12
+
+
+@pytest.mark.parametrize('name,slope', [('elu', 1.0), ('selu', K.SELU_SCALE)])
+def test_exponential_units_have_finite_gradients_at_large_inputs(name, slope):
+    """The branch torch.where drops must not overflow: at z = 100 exp(z) is inf in fp32, and an
+    unclamped expm1 there turns the whole gradient into NaN."""
+    for dtype in (torch.float32, torch.float64):
+        z = torch.tensor([-800.0, -3.0, -0.0, 0.5, 100.0, 800.0], dtype=dtype, requires_grad=True)
+        a = K.activation(name, z)
+        g, = torch.autograd.grad(a.sum(), z)
+        assert torch.isfinite(a).all() and torch.isfinite(g).all()
+        np.testing.assert_allclose(g[3:].numpy(), slope, rtol=1e-6)
+        zn = z.detach()[:3]
+        want = slope * (K.SELU_ALPHA if name == 'selu' else 1.0) * torch.exp(zn)
+        np.testing.assert_allclose(g[:3].numpy(), want.numpy(), rtol=1e-6)

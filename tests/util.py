@@ -64,3 +64,42 @@ def oracle_step(mc, w, x, y, layout, seed, image_offset=0, dtype=None):
 def data_grad64(mc, w, x, y, layout, seed, image_offset=0):
     """float64 oracle gradient of the data term (mse) in the engine's flat parameter order."""
     return oracle_step(mc, w, x, y, layout, seed, image_offset)[0]
+
+
+def check_gradient(tag, mc, w, eng, g, x, y, seed, img_off=0):
+    """The kernel's gradient g (n_train + 4 words; eng: its Engine) against the float64 oracle on
+    (x, y) in batch order with the dropout masks of (seed, img_off): whole-gradient bar 1e-5, every
+    parameter tensor normwise over itself within max(1e-5, 4 x the fp32 oracle's error), a tensor
+    whose float64 gradient is zero exactly zero, both loss sums at rtol 1e-5.  Returns the worst
+    tensor's (kernel error, fp32-oracle error, name)."""
+    import time
+    import torch
+    t0 = time.time()
+    g64, sse, sae = oracle_step(mc, w, x, y, eng.layout, seed, image_offset=img_off)
+    g32 = oracle_step(mc, w, x, y, eng.layout, seed, image_offset=img_off, dtype=torch.float32)[0]
+    npt = eng.n_train
+    assert g.shape[0] == npt + 4 and g64.shape[0] == npt
+    assert np.isfinite(g).all()
+    err = np.abs(g[:npt] - g64).max() / np.abs(g64).max()
+    worst = (0.0, 0.0, '')
+    fails = []
+    for k, (o, shp) in eng.layout.param_index.items():
+        sl = slice(o, o + int(np.prod(shp)))
+        scale = np.abs(g64[sl]).max()
+        if scale == 0.0:
+            if np.any(g[sl] != 0.0):
+                fails.append((k, 'float64 gradient is zero, kernel max |g| = %.2e' % np.abs(g[sl]).max()))
+            continue
+        ek = np.abs(g[sl] - g64[sl]).max() / scale
+        e32 = np.abs(g32[sl] - g64[sl]).max() / scale
+        if ek > worst[0]:
+            worst = (ek, e32, k)
+        if ek > max(1e-5, 4 * e32):
+            fails.append((k, 'kernel %.2e, fp32 oracle %.2e' % (ek, e32)))
+    print('%s: max |g - g64| / max |g64| = %.2e; worst tensor %s: kernel %.2e, fp32 oracle %.2e (oracle %.1f s)'
+          % (tag, err, worst[2], worst[0], worst[1], time.time() - t0))
+    assert err <= 1e-5, err
+    assert not fails, fails
+    np.testing.assert_allclose(g[npt], sse, rtol=1e-5)
+    np.testing.assert_allclose(g[npt + 1], sae, rtol=1e-5)
+    return worst
