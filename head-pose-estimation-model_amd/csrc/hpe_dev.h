@@ -1,6 +1,9 @@
 // hpe_dev.h — device helpers shared by the fused regressor kernels (hpe_mlp2.hip, hpe_fit.hip):
 // LDS-DMA staging, an LDS-only workgroup barrier, and the layer-1 activations of the hot loops.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "hpe_common.h"
 
 // LDS-DMA (global_load_lds) in inline asm: hipcc's waitcnt pass cannot tell the two X buffers
@@ -36,6 +39,55 @@ __device__ __forceinline__ void bar_lds() {
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+
+// DPP row broadcast folded into the consuming VALU op (VOP2 DPP, row_newbcast:N): every lane of a
+// 16-lane row takes lane N of its own row as the op's first source — a table that a lane half shares
+// sits one entry per lane in a VGPR and costs neither an LDS read nor a separate move per use (hipcc
+// emits a v_mov_b32_dpp per use from __builtin_amdgcn_update_dpp, hence the asm).  tests/
+// test_gpu_bcast_probe.py holds the instruction's meaning through hpe_bcast_probe.  Rules of use:
+//   * EXEC all ones (a disabled source lane reads as zero);
+//   * a VALU write of the table register followed by its DPP read needs two wait states, which hipcc
+//     does not pad around an asm statement: dpp_settle3 between the table's definition and its uses
+//     (an LDS read's s_waitcnt does not cover a register copy the allocator may put behind it)
+__device__ __forceinline__ void dpp_settle3(float& a, float& b, float& c) {
+  asm volatile("s_nop 1" : "+v"(a), "+v"(b), "+v"(c));
+}
+// one instruction: d = fma(bcast_n(t), x, d) / d = bcast_n(t) * x, operands by asm operand number
+#define HPE_DPP_CTRL(n) " row_newbcast:%c" #n " row_mask:0xf bank_mask:0xf\n\t"
+#define HPE_FMAC_BCAST(d, t, x, n) "v_fmac_f32_dpp %" #d ", %" #t ", %" #x HPE_DPP_CTRL(n)
+#define HPE_MUL_BCAST(d, t, x, n) "v_mul_f32_dpp %" #d ", %" #t ", %" #x HPE_DPP_CTRL(n)
+template <int N>
+__device__ __forceinline__ float fmac_bcast(float acc, float t, float x) {
+  asm(HPE_FMAC_BCAST(0, 1, 2, 3) : "+v"(acc) : "v"(t), "v"(x), "i"(N));
+  return acc;
+}
+template <int N>
+__device__ __forceinline__ float mul_bcast(float t, float x) {
+  float r;
+  asm(HPE_MUL_BCAST(0, 1, 2, 3) : "=v"(r) : "v"(t), "v"(x), "i"(N));
+  return r;
+}
+// the same instructions in the groups the fused kernel issues (one statement per group: hipcc pads
+// every asm statement whose result the next one reads with an s_nop of its own)
+// s_j = fma(bcast_{K + e}(t_j), a[e], s_j) for e = 0 .. 3, j = 0 .. 2 (e outer)
+template <int K>
+__device__ __forceinline__ void fmac3x4_bcast(float& s0, float& s1, float& s2, float t0, float t1, float t2, f32x4 a) {
+  asm(HPE_FMAC_BCAST(0, 3, 6, 10) HPE_FMAC_BCAST(1, 4, 6, 10) HPE_FMAC_BCAST(2, 5, 6, 10)
+      HPE_FMAC_BCAST(0, 3, 7, 11) HPE_FMAC_BCAST(1, 4, 7, 11) HPE_FMAC_BCAST(2, 5, 7, 11)
+      HPE_FMAC_BCAST(0, 3, 8, 12) HPE_FMAC_BCAST(1, 4, 8, 12) HPE_FMAC_BCAST(2, 5, 8, 12)
+      HPE_FMAC_BCAST(0, 3, 9, 13) HPE_FMAC_BCAST(1, 4, 9, 13) HPE_FMAC_BCAST(2, 5, 9, 13)
+      : "+v"(s0), "+v"(s1), "+v"(s2)
+      : "v"(t0), "v"(t1), "v"(t2), "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "i"(K), "i"(K + 1), "i"(K + 2), "i"(K + 3));
+}
+// f(integral_constant<int, I>) for I = B .. B + N - 1, in order (the DPP lane is an immediate)
+template <int B, int... I, class Fn>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, Fn&& f) {
+  (f(std::integral_constant<int, B + I>{}), ...);
+}
+template <int B, int N, class Fn>
+__device__ __forceinline__ void static_for(Fn&& f) {
+  static_for_seq<B>(std::make_integer_sequence<int, N>{}, f);
 }
 
 // activation of layer 1 fixed at compile time (tanh: Model-96, softsign: Model-88); ACT1 = -1 is

@@ -367,6 +367,9 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
   // (The W2 table packed the same way for the head partials, twelve reads for sixteen, measured
   // inside the noise and is not kept: DESIGN.md)
   constexpr bool DZ2P = PRE && MLP2_BIG_OBJ;
+  // BCH (big object): the head partials take their W2 rows by DPP row broadcast, one table read per tile
+  // (the small object's step lines were not measured with it and keep the sixteen broadcast reads)
+  constexpr bool BCH = PRE && MLP2_BIG_OBJ;
   constexpr int DZS = DZ2P ? 3 : 4;
 
   E2 e1 = {o[O_EACT], o[O_EDROP], (uint32_t)o[O_ETHR], __int_as_float(o[O_EKEEP])};
@@ -668,6 +671,20 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
         const float* ar = a1s + wave * A1S + (PAD1 ? a1_row(gr) : 64 * gr) + hh * 32 + 16 * thalf;
         const float* wr = w2t + (wave * 32 + 16 * thalf) * 4;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        if constexpr (BCH) {
+          // the half's sixteen W2 rows one per lane (lane 16 q + u of the wave: unit 16 (q >> 1) + u),
+          // handed to the FMAs by row broadcast: one table read where sixteen broadcast reads stood
+          f32x4 av[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) av[i] = *(const f32x4*)(ar + 4 * i);
+          const f32x4 wq = *(const f32x4*)(wr + (tlane & 15) * 4);
+          float wx = wq.x, wy = wq.y, wz = wq.z;
+          dpp_settle3(wx, wy, wz);
+          fmac3x4_bcast<0>(s0, s1, s2, wx, wy, wz, av[0]);
+          fmac3x4_bcast<4>(s0, s1, s2, wx, wy, wz, av[1]);
+          fmac3x4_bcast<8>(s0, s1, s2, wx, wy, wz, av[2]);
+          fmac3x4_bcast<12>(s0, s1, s2, wx, wy, wz, av[3]);
+        } else {
 #pragma unroll
         for (int i = 0; i < 16; i += 4) {
           const f32x4 av = *(const f32x4*)(ar + i);
@@ -678,6 +695,7 @@ __global__ void __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(N
             s1 = fmaf(av[e], w.y, s1);
             s2 = fmaf(av[e], w.z, s2);
           }
+        }
         }
         if constexpr (PRE) {
           s0 += xor32_now(s0, tlane);

@@ -1123,6 +1123,28 @@ extern "C" int hpe_act_probe(int32_t act, int32_t fast, const float* z, float* o
   return e == hipSuccess ? HPE_OK : hpe_fail(HPE_ERUNTIME, "act_probe launch: %s", hipGetErrorString(e));
 }
 
+// hpe_bcast_probe: the DPP row-broadcast helpers of hpe_dev.h (fmac_bcast / mul_bcast) as one wave
+// evaluates them, every N = 0 .. 15: out[0][N][lane] = fma(bcast_N(t), x[lane], acc[lane]),
+// out[1][N][lane] = bcast_N(t) * x[lane] — tests/test_gpu_bcast_probe.py holds bcast_N(t) to
+// t[(lane & ~15) + N]
+__global__ void __launch_bounds__(64) bcast_probe_kernel(const float* t, const float* x, const float* acc, float* out) {
+  const int lane = threadIdx.x;
+  float tv = t[lane], xv = x[lane], av = acc[lane];
+  dpp_settle3(tv, xv, av);
+  static_for<0, 16>([&](auto ni) {
+    constexpr int N = decltype(ni)::value;
+    out[N * 64 + lane] = fmac_bcast<N>(av, tv, xv);
+    out[(16 + N) * 64 + lane] = mul_bcast<N>(tv, xv);
+  });
+}
+
+extern "C" int hpe_bcast_probe(const float* t, const float* x, const float* acc, float* out, void* stream) {
+  if (!t || !x || !acc || !out) return hpe_fail(HPE_EINVAL, "bcast_probe: bad argument");
+  hipLaunchKernelGGL(bcast_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, x, acc, out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HPE_OK : hpe_fail(HPE_ERUNTIME, "bcast_probe launch: %s", hipGetErrorString(e));
+}
+
 extern "C" int hpe_set_exact_fp32(int on) {
   const int prev = hpe_exact_fp32() ? 1 : 0;
   g_exact = on ? 1 : 0;

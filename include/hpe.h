@@ -629,6 +629,12 @@ int hpe_set_exact_fp32(int on);
  * (tanh: tanhf).  Device pointers, n floats; asynchronous on `stream`. */
 int hpe_act_probe(int32_t act, int32_t fast, const float *z, float *out, int64_t n, void *stream);
 
+/* Diagnostics: the DPP row-broadcast operand of the fused regressor kernel (csrc/hpe_dev.h
+ * fmac_bcast / mul_bcast) as one 64-lane wave evaluates it.  t, x, acc: 64 floats each; out: [2][16][64]
+ * floats, out[0][N][lane] = fma(t[(lane & ~15) + N], x[lane], acc[lane]) and out[1][N][lane] =
+ * t[(lane & ~15) + N] * x[lane].  Device pointers; asynchronous on `stream`. */
+int hpe_bcast_probe(const float *t, const float *x, const float *acc, float *out, void *stream);
+
 /* Attention heads on H x W > 1 feature maps: the two stages that are not
  * row-local.  Replace the TF kernels behind GlobalAveragePooling2D -> Dense -> Dense -> Multiply
  * (Model-88/attention_model.py:34-38, :78-82) and behind MultiHeadAttention's softmax(QK^T)V over
